@@ -17,7 +17,10 @@ Synthetic data: splitmix64 TS packets (dvbt2ll.configs).
 Steps are pipelined: the chain handle holds --slots intermediate buffer sets and step s is
 issued on HIP stream s % slots (dvbt2ll_chain_set_slots), so consecutive steps overlap on the GPU.
 
-Extra fields: roofline (dominant kernel, HIP-event timed on the launch stream inside a serial
+A plain run sets up, warms up, times the --steps pipelined steps, writes the last step's IQ if
+--dump-outputs is given, and prints the headline line.  Everything below runs only with --full.
+
+Extra fields (--full): roofline (dominant kernel, HIP-event timed on the launch stream inside a serial
 timed pass of the same K steps on one stream -- per-kernel event durations mean nothing under
 cross-stream overlap; traffic from rocprofv3 PMC passes run as child processes BEFORE this
 process touches the GPU), serial_1_stream (that pass's rate) and cpu_baseline (the oracle C
@@ -53,6 +56,15 @@ def parse():
                          "launch; 640 / 768 / 896 / 1152 / 1280 / 1344 frames per step measured 218.6 / 223.6 / "
                          "223.6 / 227.6 / 227.4 / 227.7 G IQ samples/s on one box, profiles/r4_frames_sweep.txt)")
     ap.add_argument("--config", default="cfg3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline pass, also run every secondary measurement (rocprofv3 PMC passes, the "
+                         "serial pass with per-stage timings and rooflines, sc16, latency, per-block, multi-PLP, "
+                         "host-delivered, gather, CPU baseline, IQ accuracy); each can be skipped with its --no-* "
+                         "option.  Without --full only the headline pass runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the IQ the last timed step produced as DIR/iq.npy (float32, "
+                         "[samples, 2] = I, Q; rank r > 0 writes iq_rank<r>.npy): the whole buffer if it is at most "
+                         "48 MB, else a fixed seeded sample of its complex samples")
     ap.add_argument("--no-pmc", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sc16", action="store_true", help="skip the secondary sc16-output timing")
@@ -592,6 +604,29 @@ def host_delivered(cfg, chunk, chunks, peaks):
     return out
 
 
+DUMP_WHOLE_BYTES = 48 << 20    # --dump-outputs: an IQ buffer up to this size is written whole
+DUMP_SAMPLES = 4 << 20         # else this many of its complex samples (32 MB of float32 I, Q)
+
+
+def dump_outputs(path, iq, rank):
+    """--dump-outputs: the IQ buffer ([samples, 2] float32 in HBM) a caller of the timed step receives, as
+    DIR/iq.npy.  A buffer above DUMP_WHOLE_BYTES is sampled: DUMP_SAMPLES sample indices drawn once from a
+    generator seeded with the buffer's length, sorted, so two builds given the same arguments write the
+    same samples of the same frames"""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    n = iq.shape[0]
+    if iq.numel() * iq.element_size() > DUMP_WHOLE_BYTES:
+        g = torch.Generator()
+        g.manual_seed(n)
+        idx = torch.randint(0, n, (DUMP_SAMPLES,), generator=g, dtype=torch.int64).sort().values
+        iq = iq.index_select(0, idx.to(iq.device))
+    arr = iq.cpu().numpy().astype(np.float32, copy=False)
+    np.save(os.path.join(path, "iq.npy" if rank == 0 else "iq_rank%d.npy" % rank), arr)
+
+
 def hbm_footprint(info, B, S, R, world, ts_len, sc16, gather_frames):
     """bytes the bench allocates in HBM per rank (rank 0 holds the gather's output too): the chain's S buffer
     slots (codewords, BCH partials, index pairs, L1 cells), S complex64 IQ buffers (+ S sc16 ones while the
@@ -633,7 +668,7 @@ def spawn_ranks(args):
     touches the GPU (it never does) -- and rank 0's JSON line relayed.  Any rank failing fails the run."""
     n = args.gpus
     env0 = dict(os.environ)
-    if not args.dry_run and not args.no_pmc:
+    if not args.dry_run and args.full and not args.no_pmc:
         traffic, note = pmc_passes(args)
         fd, path = tempfile.mkstemp(prefix="t2pmc_", suffix=".json", dir=os.environ.get("TMPDIR", "/tmp"))
         with os.fdopen(fd, "w") as fh:
@@ -794,7 +829,7 @@ def main():
         with open(os.environ["DVBT2LL_BENCH_PMC_JSON"]) as fh:
             pm = json.load(fh)
         traffic, pmc_note = pm["traffic"], pm["note"]
-    elif world == 1 and not args.pmc_child and not args.no_pmc:
+    elif world == 1 and not args.pmc_child and args.full and not args.no_pmc:
         traffic, pmc_note = pmc_passes(args)          # before any GPU initialisation here
     elif world > 1:
         pmc_note = "not collected under an external launcher (bench.py --gpus N spawns its ranks after its PMC passes)"
@@ -839,7 +874,7 @@ def main():
     S = max(1, args.slots)
     # the default shapes must fit HBM at N = 8 too (rank 0 also holds the ordered gather's output)
     G = min(B, 512)
-    need = hbm_footprint(info, B, S, R, world, max(m[2] for m in ts_meta), not args.no_sc16, G)
+    need = hbm_footprint(info, B, S, R, world, max(m[2] for m in ts_meta), args.full and not args.no_sc16, G)
     if need > 0.9 * HBM_BYTES:
         raise SystemExit("bench.py: %.1f GB of HBM needed per rank, more than 90 %% of %.0f GB" % (need / 1e9,
                                                                                               HBM_BYTES / 1e9))
@@ -896,6 +931,38 @@ def main():
     # K steps (all on one stream) right after it
     # (with one slot too: the headline pass never records the per-stage timing events, which cost ~3 % of a step)
     elapsed, _ = timed()
+    if args.dump_outputs:
+        # the last timed step's IQ, before any secondary pass reuses the buffers
+        dump_outputs(args.dump_outputs, out[0][(args.steps - 1) % S], rank)
+    frames_total = B * args.steps * world
+    samples_total = frames_total * per
+    fec_total = frames_total * info["fec_blocks_per_frame"]
+    msps = samples_total / elapsed / 1e6
+    head = {
+        "metric": metric_for(args.config), "value": msps, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "%s: TS->IQ full DVB-T2 chain, %d T2 frames per step per GPU%s "
+                               "(%d FEC blocks, %d IQ samples per frame)"
+                               % (cfg.name, B, " (%d independent TS streams x %d frames, one launch)" % (NS, BS)
+                                  if NS > 1 else "", info["fec_blocks_per_frame"], per),
+                   "frames_per_step_per_gpu": B, "slots_streams_per_gpu": S,
+                   "symbols_per_frame": info["num_symbols"], "fft_size": info["fft_size"],
+                   "guard_samples": info["guard_interval"],
+                   "ts_streams_per_launch": NS,
+                   "parallelism": "%s x%d (no data-path collective)"
+                                  % ("frame-sharded" if args.shard == "frames" else "independent streams", world),
+                   "launcher": "bench.py spawn" if os.environ.get("DVBT2LL_BENCH_SPAWNED") else
+                               ("external" if world > 1 else "single process")},
+        "fec_blocks_per_sec": fec_total / elapsed,
+        "x_realtime": msps * 1e6 / RT_SPS,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if dist:
+            dist.destroy_process_group()
+        return
     serial_elapsed, (stage_ms, launches) = timed(serial=True, timing=True)
     # secondary line (not `value`): the same chain with the flowgraph's output step fused into the
     # IQ store (x0.2 gain, sc16 wire format: 4 B per sample instead of 8)
@@ -952,10 +1019,6 @@ def main():
                     "note": "secondary: every step (all B frames encoded) followed by the ordered gather of its "
                             "first G frames' complex64 IQ per rank to rank 0 (dvbt2ll.distributed.gather_frames, "
                             "grouped send/recv); not `value`"}
-    frames_total = B * args.steps * world
-    samples_total = frames_total * per
-    fec_total = frames_total * info["fec_blocks_per_frame"]
-    msps = samples_total / elapsed / 1e6
     if rank == 0:
         ab = algorithmic_bytes(cfg, info)
         mb = minimal_bytes(cfg, info)
@@ -1006,32 +1069,16 @@ def main():
                         "SURVEY 8(d)'s unfused stage bytes over the same time (not an HBM utilisation)")
         if traffic is None:
             roof["traffic_note"] = pmc_note
-        out = {
-            "metric": metric_for(args.config), "value": msps, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s: TS->IQ full DVB-T2 chain, %d T2 frames per step per GPU%s "
-                                   "(%d FEC blocks, %d IQ samples per frame)"
-                                   % (cfg.name, B, " (%d independent TS streams x %d frames, one launch)" % (NS, BS)
-                                      if NS > 1 else "", info["fec_blocks_per_frame"], per),
-                       "frames_per_step_per_gpu": B, "slots_streams_per_gpu": S,
-                       "symbols_per_frame": info["num_symbols"], "fft_size": info["fft_size"],
-                       "guard_samples": info["guard_interval"],
-                       "ts_streams_per_launch": NS,
-                       "parallelism": "%s x%d (no data-path collective)"
-                                      % ("frame-sharded" if args.shard == "frames" else "independent streams", world),
-                       "launcher": "bench.py spawn" if os.environ.get("DVBT2LL_BENCH_SPAWNED") else
-                                   ("external" if world > 1 else "single process")},
-            "fec_blocks_per_sec": fec_total / elapsed,
+        out = dict(head)
+        out.update({
             "serial_1_stream": {"value": samples_total / serial_elapsed / 1e6,
                                 "ms_per_step": serial_elapsed / args.steps * 1e3,
                                 "note": "same K steps issued on one stream (no cross-step overlap); the "
                                         "stage timings and roofline come from this pass"},
-            "x_realtime": msps * 1e6 / RT_SPS,
             "stages": stages,
             "roofline": roof,
             "rooflines": rooflines,
-        }
+        })
         # chain level (per GPU): the bytes the step cannot avoid (TS payload in, IQ out) and the bytes the PMC
         # passes counted (each stage's calibrated FETCH + WRITE per launch x its launches per step), over the
         # pipelined step time; the serial kernel sum beside the pipelined step is what the slots overlap

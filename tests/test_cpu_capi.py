@@ -48,6 +48,23 @@ def test_no_cpu_fallback_without_gpu():
         dvbt2ll.Chain(dvbt2ll.CONFIGS["cfg1"], max_frames=1)
 
 
+def test_gr_adapter_driver_compiles_against_generated_block_headers(tmp_path):
+    """where gr-dvbt2ll's public headers are not installed, build() compiles the driver against the block
+    declarations tests/adapter/gen_gr_api.py derives from the adapters and dvbt2ll/enums.py: that path
+    compiles, whichever headers this machine's build() used"""
+    import subprocess
+    import sys
+    root = Path(__file__).resolve().parents[1]
+    subprocess.run([sys.executable, str(root / "tests" / "adapter" / "gen_gr_api.py"), str(tmp_path)], check=True)
+    assert sorted(p.name for p in (tmp_path / "dvbt2ll").iterdir()) == [
+        "bbheaderbch_bb.h", "dvbt2ll_config.h", "framemapperfint_cc.h", "interleavermod_bc.h",
+        "pilotgenp1insert_cc.h"]
+    r = subprocess.run(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-Wextra", "-Wno-unused-parameter",
+                        "-I" + str(root / "tests" / "gr_stub"), "-I" + str(tmp_path), "-I" + str(root / "include"),
+                        str(root / "tests" / "adapter" / "gr_flowgraph.cpp")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
 def test_gr_adapter_driver_built_and_fails_cleanly_without_gpu(tmp_path):
     """the header-only GNU Radio adapters compile (build() makes tests/adapter/gr_flowgraph against
     the stand-in GR headers); without a GPU, make() throws and the driver exits 1 with the ABI's error"""

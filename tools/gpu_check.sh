@@ -14,6 +14,6 @@ rc=$?
 tail -30 "$O/pytest.log"
 [ $rc = 0 ] || exit $rc
 [ -n "$NOBENCH" ] && exit 0
-timeout -k 10 240 python bench.py --no-pmc --no-cpu-baseline --no-latency --no-sc16 --no-blocks --steps 20 --warmup 3 \
+timeout -k 10 240 python bench.py --full --no-pmc --no-cpu-baseline --no-latency --no-sc16 --no-blocks --steps 20 --warmup 3 \
   $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 python -c "import json; d=json.load(open('$O/bench.json')); print({k: round(s['avg_launch_ms'],4) for k,s in d['stages'].items()}, round(d['value']))"

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/$1; shift; mkdir -p "$O"
 timeout -k 10 300 rocprofv3 --kernel-trace -d "$O/otrace" -o otrace -f csv -- \
-  python bench.py --no-pmc --no-cpu-baseline --no-latency --no-sc16 --no-blocks --no-host --no-mplp --steps 10 --warmup 2 "$@" \
+  python bench.py --full --no-pmc --no-cpu-baseline --no-latency --no-sc16 --no-blocks --no-host --no-mplp --steps 10 --warmup 2 "$@" \
   > "$O/otrace_bench.json" 2> "$O/otrace.err" || { tail -20 "$O/otrace.err"; exit 1; }
 f=$(find "$O/otrace" -name '*kernel_trace.csv' | head -1)
 cp "$f" "$O/otrace_kernel_trace.csv"

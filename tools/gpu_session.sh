@@ -17,10 +17,10 @@ step tests && IQ_STATS=$PWD/$O/iq_stats.jsonl timeout -k 10 900 python -u -m pyt
   && step smoke && timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 \
   && cat "$O/smoke.log" || { rc=$?; tail -30 "$O/pytest.log"; exit $rc; }
 [ -n "$NOBENCH" ] && exit 0
-step bench && timeout -k 10 900 python -u bench.py $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" \
+step bench && timeout -k 10 900 python -u bench.py --full $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" \
   && cat "$O/bench.json" || { rc=$?; tail -20 "$O/bench.err"; exit $rc; }
 [ -n "$NOTRACE" ] && exit 0
 step trace && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/trace" -o trace -f csv -- \
-     python bench.py --no-pmc --no-cpu-baseline --no-latency --no-sc16 --no-blocks --no-mplp --no-host --slots 1 --steps 10 --warmup 2 \
+     python bench.py --full --no-pmc --no-cpu-baseline --no-latency --no-sc16 --no-blocks --no-mplp --no-host --slots 1 --steps 10 --warmup 2 \
      > "$O/trace_bench.json" 2> "$O/trace.err" \
   && echo "=== done ($(date +%T))"
