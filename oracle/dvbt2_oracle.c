@@ -201,6 +201,7 @@ struct orc_bb {
   unsigned count;
   uint8_t crc;
   int extra;
+  long sync_errors;                  /* the reference's "Transport Stream sync error!" warnings (bbheader:675-677, 703-705) */
   uint8_t crc_tab[256];
   uint8_t bb_randomise[FRAME_SIZE_NORMAL];
   r192 tab[256];
@@ -260,6 +261,7 @@ orc_bb *orc_bb_create(int framesize, int rate, int mode, int inband, int fecbloc
 void orc_bb_set_isi(orc_bb *h, int isi) { h->sis_mis = 0; h->isi = isi & 0xFF; }
 int orc_bb_nbch(const orc_bb *h) { return h->nbch; }
 int orc_bb_kbch(const orc_bb *h) { return h->kbch; }
+long orc_bb_sync_errors(const orc_bb *h) { return h->sync_errors; }
 void orc_bb_destroy(orc_bb *h) { free(h); }
 
 /* forecast (bbheader:207-216) */
@@ -319,7 +321,7 @@ int orc_bb_work(orc_bb *h, int nout, const uint8_t *in, uint8_t *out, int *consu
     int npay = (h->kbch - 80 - padding) / 8;
     if (h->mode == INPUTMODE_HIEFF) {
       for (int j = 0; j < npay; j++) {
-        if (h->count == 0) { j--; in++; }   /* sync byte dropped (warning if != 0x47) */
+        if (h->count == 0) { if (*in != 0x47) h->sync_errors++; j--; in++; }   /* sync byte dropped (warning if != 0x47) */
         else { uint8_t b = *in++; for (int n = 7; n >= 0; n--) out[off++] = (b >> n) & 1; }
         h->count = (h->count + 1) % 188;
         consumed++;
@@ -327,7 +329,7 @@ int orc_bb_work(orc_bb *h, int nout, const uint8_t *in, uint8_t *out, int *consu
     } else {
       for (int j = 0; j < npay; j++) {
         uint8_t b;
-        if (h->count == 0) { in++; b = h->crc; h->crc = 0; }
+        if (h->count == 0) { if (*in != 0x47) h->sync_errors++; in++; b = h->crc; h->crc = 0; }
         else { b = *in++; h->crc = h->crc_tab[b ^ h->crc]; }
         h->count = (h->count + 1) % 188;
         consumed++;

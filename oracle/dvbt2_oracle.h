@@ -38,6 +38,9 @@ int orc_bb_kbch(const orc_bb *h);
 int orc_bb_forecast(const orc_bb *h, int noutput_items);
 /* returns noutput_items; *consumed = input bytes consumed */
 int orc_bb_work(orc_bb *h, int noutput_items, const uint8_t *in, uint8_t *out, int *consumed);
+/* consumed sync bytes != 0x47 so far: one per "Transport Stream sync error!" warning of the reference
+ * (bbheader:675-677, 703-705) */
+long orc_bb_sync_errors(const orc_bb *h);
 /* one PLP of a multi-PLP frame: MATYPE SIS/MIS = multiple, MATYPE-2 ISI = isi (the PLP_ID;
  * bbheader:288-298).  Parity unpinned (the reference's ctor fixes SIS, :168). */
 void orc_bb_set_isi(orc_bb *h, int isi);

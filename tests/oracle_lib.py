@@ -31,6 +31,8 @@ def lib():
         L.orc_bb_kbch.argtypes = [vp]
         L.orc_bb_destroy.argtypes = [vp]
         L.orc_bb_set_isi.argtypes = [vp, ci]
+        L.orc_bb_sync_errors.restype = ctypes.c_long
+        L.orc_bb_sync_errors.argtypes = [vp]
         L.orc_fm_create_mplp.restype = vp
         L.orc_fm_create_mplp.argtypes = [ci, vp] + [ci] * 13
         L.orc_fm_consume.argtypes = [vp, ci]
@@ -95,6 +97,10 @@ class BB:
         c = ctypes.c_int(0)
         lib().orc_bb_work(self.h, nblocks * self.nbch, _p(ts), _p(out), ctypes.byref(c))
         return out, c.value
+
+    def sync_errors(self):
+        """consumed sync bytes != 0x47 so far (the reference's "Transport Stream sync error!" warnings)"""
+        return int(lib().orc_bb_sync_errors(self.h))
 
     def __del__(self):
         if getattr(self, "h", None):

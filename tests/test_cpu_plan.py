@@ -345,9 +345,13 @@ def test_bch_lane_shift_tables(framesize, rate):
 @pytest.mark.parametrize("framesize,rate", [(1, r) for r in range(6)] + [(0, r) for r in range(8)])
 def test_bch_matrix_core_table(framesize, rate):
     """The chain's BCH (t2_kernels.hip bbch_kernel) computes every block's parity as a GF(2)
-    matrix product on the matrix cores: fp4 A fragments masked from the message words, fp4 B fragments
-    from the planner table (build_bch_mfma), exact sums, parity = sum & 1, K split into slices whose
-    partial parities are XORed (BCH_KS = 8).  Replayed here with the kernel's operand pairing (lane half h,
+    matrix product on the matrix cores: fp4 A fragments that are the message words themselves, masked in
+    place (A dword d keeps bit d of every nibble where it stands, so a set bit reads as the fp4 value 0.5,
+    1.0 or 2.0; bit 3 is fp4's sign, so d = 3 is moved down one and reads 2.0), fp4 B fragments from the
+    planner table (build_bch_mfma) whose set entries are the reciprocals 2.0, 1.0, 0.5, 0.5, so every
+    product of two set bits is exactly 1; exact sums, parity = sum & 1, K split into slices whose partial
+    parities are XORed (the kernel's BCH_KS = 2; the replay below XORs 8 slices, a finer split of the same
+    GF(2) sum).  Replayed here with the kernel's operand pairing (lane half h,
     K-step u, A dword d, nibble e: bit 4 e + d of the little-endian word of message bytes 32 q + 16 h + 4 u
     .. + 3; column = lane & 31 of tile t) on random
     messages whose bytes past the BBFRAME are garbage (the kernel reads them and must ignore them);
