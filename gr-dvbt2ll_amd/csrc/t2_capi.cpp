@@ -473,7 +473,23 @@ extern "C" void dvbt2ll_framemapperfint_destroy(dvbt2ll_framemapperfint *h) { de
 
 // ============================================================================ framemapper, multi-PLP
 static bool mplp_to_plan(const dvbt2ll_mplp_params &m, FmParams &fm, std::vector<PlpParams> &plps,
-                         std::vector<int> &tsrate, int *nss);
+                         std::vector<int> &tsrate, int *nss) {
+  if (m.nplp < 1 || m.nplp > DVBT2LL_MAX_PLP) return false;
+  const dvbt2ll_plp_params &q0 = m.plp[0];
+  fm = FmParams{q0.framesize, q0.rate, q0.constellation, q0.rotation, q0.fecblocks, q0.tiblocks, m.carriermode,
+                m.fftsize, m.guardinterval, m.l1constellation, m.pilotpattern, m.t2frames, m.numdatasyms, m.paprmode,
+                m.version, m.preamble, q0.inputmode, m.reservedbiasbits, m.l1scrambled, q0.inband};
+  plps.clear();
+  tsrate.clear();
+  for (int k = 0; k < m.nplp; k++) {
+    const dvbt2ll_plp_params &q = m.plp[k];
+    plps.push_back(PlpParams{q.framesize, q.rate, q.constellation, q.rotation, q.fecblocks, q.tiblocks, q.inputmode,
+                             q.inband, q.plp_type, q.ti_type, q.ti_frames, q.frame_interval, q.first_frame_idx});
+    tsrate.push_back(q.tsrate);
+  }
+  *nss = m.num_subslices;
+  return true;
+}
 
 struct dvbt2ll_framemapper_mplp {
   DeviceCtx ctx;
@@ -681,7 +697,7 @@ struct ChainPlp {
   int64_t blocks(int64_t frames) const { return (frames + cyc - 1) / cyc * F; }   // FEC blocks of `frames` T2 frames
 };
 
-// instantiated hipGraphs of the chain's kernels (per PLP: FEC BB pass, BCH matrix-core pass; per PLP: LDPC +
+// instantiated hipGraphs of the chain's kernels (per PLP: bbch_kernel, BBFRAMEs + matrix-core BCH; per PLP: LDPC +
 // map (PLP 0's launch also generates the L1-post); OFDM) for one (nframes, IQ format, slot),
 // captured once from the ordinary launch path into a ring of instantiations.  A call takes the next
 // ring entry, waits for it only if it is still in flight, rewrites its kernel nodes' arguments
@@ -833,9 +849,9 @@ struct dvbt2ll_chain {
     evused = 0;
     return st;
   }
-  // the chain's kernels on stream s: every PLP's BB + matrix-core BCH passes, every PLP's LDPC + map
+  // the chain's kernels on stream s: every PLP's BB + matrix-core BCH kernel, every PLP's LDPC + map
   // (PLP 0's launch has the extra workgroups that generate the frames' L1-post cells), OFDM.  ev1, ev2
-  // (timing): recorded after the BB + BCH passes and after the LDPC + map kernels
+  // (timing): recorded after the BB + BCH kernels and after the LDPC + map kernels
   hipError_t launch_chain(const L1IO &lio, const FecIO *fio, const MapIO *mio, const OfdmIO &oio, hipStream_t s,
                           hipEvent_t ev1, hipEvent_t ev2) {
     hipError_t e = hipSuccess;
@@ -1227,25 +1243,6 @@ extern "C" int dvbt2ll_chain_create(const dvbt2ll_chain_params *p, int device, d
   if (r) return r;
   *out = h.release();
   return DVBT2LL_OK;
-}
-
-static bool mplp_to_plan(const dvbt2ll_mplp_params &m, FmParams &fm, std::vector<PlpParams> &plps,
-                         std::vector<int> &tsrate, int *nss) {
-  if (m.nplp < 1 || m.nplp > DVBT2LL_MAX_PLP) return false;
-  const dvbt2ll_plp_params &q0 = m.plp[0];
-  fm = FmParams{q0.framesize, q0.rate, q0.constellation, q0.rotation, q0.fecblocks, q0.tiblocks, m.carriermode,
-                m.fftsize, m.guardinterval, m.l1constellation, m.pilotpattern, m.t2frames, m.numdatasyms, m.paprmode,
-                m.version, m.preamble, q0.inputmode, m.reservedbiasbits, m.l1scrambled, q0.inband};
-  plps.clear();
-  tsrate.clear();
-  for (int k = 0; k < m.nplp; k++) {
-    const dvbt2ll_plp_params &q = m.plp[k];
-    plps.push_back(PlpParams{q.framesize, q.rate, q.constellation, q.rotation, q.fecblocks, q.tiblocks, q.inputmode,
-                             q.inband, q.plp_type, q.ti_type, q.ti_frames, q.frame_interval, q.first_frame_idx});
-    tsrate.push_back(q.tsrate);
-  }
-  *nss = m.num_subslices;
-  return true;
 }
 
 extern "C" int dvbt2ll_chain_create_mplp(const dvbt2ll_mplp_chain_params *p, int device, dvbt2ll_chain **out) {

@@ -138,39 +138,37 @@ constexpr int FEC_MAX_ENT = 648;        // max LDPC table entries (3/5 normal: 2
 constexpr int FEC_DW = 13;              // LDS words per LDPC info group (fused kernel): d_g || d_g[0..56)
 constexpr int FEC_DW_PASS = 16;         // chain LDPC stage: d_g || d_g[0..152), four windows without wrap
 constexpr int FEC_WG_PER_CU = 7;        // fused kernel: resident workgroups per CU (72-VGPR budget)
-constexpr int FEC_PASS_WG_PER_CU = 8;   // chain BB pass, LDPC + map kernel (64-VGPR budget, 32 waves per CU)
+constexpr int LM_WG_PER_CU = 8;         // ldpc_map_kernel: workgroups per CU (64-VGPR budget, 32 waves per CU)
+constexpr int LM_ROW_UNITS = 2;         // ldpc_map_kernel: 16-byte BBFRAME units each thread loads from the row
 constexpr int FEC_BCH_JB = 2;           // nibble-table lookups in flight per lane in the BCH combine
 constexpr int FEC_LDPC_BYTES = 4 * (FEC_DW_PASS * 150 + 12 * 30); // max over codes of 64 ngroups + 48 q
 
-// dynamic LDS carve (bytes) of each FEC kernel kind: persistent tables (staged once; the
-// workgroups loop over FEC blocks), then the per-block area, reused by phase:
-//   BB phase:   [frame | raw TS bytes | CRC-8 table | CRC-8 zero-extension tables]
-//   LDPC phase: [frame | D: ngroups x 13 words | rows: q x 12 words], ngroups + q = nldpc / 360 (<= 180)
+// dynamic LDS carve (bytes) of the block kernel (CARVE_FUSED: fec_kernel, both modes) and of the chain's
+// LDPC stage (CARVE_LDPC: ldpc_map_kernel): tables (staged once), then the per-block area, reused by phase:
+//   BB phase (fused only): [frame | raw TS bytes | CRC-8 table | CRC-8 zero-extension tables]
+//   LDPC phase: [frame | D: ngroups x DW words | rows: q x 12 words], ngroups + q = nldpc / 360 (<= 180),
+//               DW = FEC_DW (fused) or FEC_DW_PASS
 // sized for the plan's code, so a launch fits as many workgroups per CU as it allows
-enum FecCarveKind { CARVE_FUSED = 0, CARVE_BB = 1, CARVE_LDPC = 2 };
+enum FecCarveKind { CARVE_FUSED = 0, CARVE_LDPC = 1 };
 struct FecCarve {
-  int btab, ents, hcrc, sync, w, rowp, frame, phase, crc8, crcsh, crcsl, prbs, total;
+  int btab, ents, hcrc, sync, w, rowp, frame, phase, crc8, crcsh, total;
 };
 __host__ __device__ inline FecCarve fec_carve(int kind, int kbch, int nbch, int q) {
   FecCarve c{};
-  const bool bch = kind == CARVE_FUSED, ldpc = kind != CARVE_BB, bb = kind != CARVE_LDPC;
+  const bool fused = kind == CARVE_FUSED;
   int o = 0;
-  c.btab = o; o += bch ? 256 * 3 * 8 : 0;
-  c.ents = o; o += ldpc ? FEC_MAX_ENT * 4 : 0;
-  c.hcrc = o; o += bb ? 80 : 0;            // 72 header-bit CRC contributions
-  c.sync = o; o += bb ? 48 : 0;            // <= 36 sync-slot CRC-8s
-  c.w = o; o += ldpc ? 48 : 0;             // 12 column-parity words
-  c.rowp = o; o += ldpc ? 192 : 0;         // q + 1 <= 91 LDPC row pointers
-  // BB pass: T^1 .. T^24 of the CRC-8 byte table T at a compile-time offset (the lookups' addresses are
-  // the byte itself plus an immediate), before the code-dependent areas
-  c.crcsl = o; o += kind == CARVE_BB ? 24 * 256 : 0;
+  c.btab = o; o += fused ? 256 * 3 * 8 : 0;   // BCH byte tables
+  c.ents = o; o += FEC_MAX_ENT * 4;
+  c.hcrc = o; o += fused ? 80 : 0;         // 72 header-bit CRC contributions
+  c.sync = o; o += fused ? 48 : 0;         // <= 36 sync-slot CRC-8s
+  c.w = o; o += 48;                        // 12 column-parity words
+  c.rowp = o; o += 192;                    // q + 1 <= 91 LDPC row pointers
   c.frame = (o + 15) & ~15;
-  c.phase = c.frame + (kind == CARVE_BB ? 0 : ((nbch / 8 + 15) & ~15));   // the BB pass stores its frame to HBM
+  c.phase = c.frame + ((nbch / 8 + 15) & ~15);
   c.crc8 = c.phase + ((188 + (kbch - 80) / 8 + 32 + 15) & ~15);   // + slack: 16-byte staging start
   c.crcsh = c.crc8 + 256;
-  c.prbs = c.crcsh + 2048;                 // BB pass: the BB-scrambler PRBS words
-  const int bb_end = c.prbs + (kind == CARVE_BB ? ((kbch / 8 + 15) & ~15) : 0), ldpc_end = c.phase + 4 * ((kind == CARVE_LDPC ? FEC_DW_PASS : FEC_DW) * (nbch / 360) + 12 * q);
-  c.total = kind == CARVE_BB ? bb_end : kind == CARVE_LDPC ? ldpc_end : (bb_end > ldpc_end ? bb_end : ldpc_end);
+  const int bb_end = c.crcsh + 2048, ldpc_end = c.phase + 4 * ((fused ? FEC_DW : FEC_DW_PASS) * (nbch / 360) + 12 * q);
+  c.total = fused && bb_end > ldpc_end ? bb_end : ldpc_end;
   return c;
 }
 
@@ -399,11 +397,6 @@ __device__ __forceinline__ uint32_t *fec_ldpc(const FecDev &d, uint32_t *D, int 
   return cur;
 }
 
-// BBFRAME of FEC block B (absolute index; the reference keeps count / crc / fec_block as running
-// state, bbheader:661-734, here they are closed-form in B) into frame[0, L): raw TS staging, the
-// sync-slot CRC-8s, BBHEADER + its CRC-8, payload words, the in-band field, BB scrambling.  Ends
-// with a barrier.  crc_resident: the CRC-8 tables already sit at cv.crc8 / cv.crcsh (the BB pass
-// stages them once; the fused kernel's LDPC area overlays them, so it reloads them per block).
 // BBFRAME geometry of absolute FEC block B, closed form (the reference keeps count / crc / fec_block
 // as running state, bbheader:661-734).  NM: the raw stream bytes [pos0 - 188, pos0 + npay) are staged
 // as nq 16-byte units from the aligned stream offset 16 w0 (raw byte i = stream byte rs + i at LDS
@@ -413,7 +406,7 @@ struct BbGeom {
   int npay, padding, count0, delta, nq;
 };
 // x mod 188 for x >= 0 from 32-bit remainders (2^32 = 136 mod 188): a 64-bit remainder by a constant is
-// a long 64-bit multiply chain on the scalar unit, and the BB pass evaluates the geometry per block
+// a long 64-bit multiply chain on the scalar unit, and the geometry is evaluated per block
 __device__ __forceinline__ int mod188(int64_t x) {
   const uint32_t hi = (uint32_t)((uint64_t)x >> 32), lo = (uint32_t)x;
   return (int)(((hi % 188u) * 136u + lo % 188u) % 188u);
@@ -449,43 +442,41 @@ __device__ __forceinline__ uint4 bb_raw_unit(const FecIO &io, const uint8_t *tin
     if (b + e >= 0 && b + e < io.ts_len) w[e >> 2] |= (uint32_t)tin[b + e] << (8 * (e & 3));
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
-constexpr int FEC_PRE = 2;   // raw units per thread a BB pass workgroup prefetches for its next block (nq <= 512)
+// byte k < 13 of the in-band type B field (bbheader:327-355): 01, 65 zero bits, the TS rate in 27 bits, 10 zero bits
+__device__ __forceinline__ uint32_t inband_byte(int k, int ts_rate) {
+  uint32_t v = k == 0 ? 0x40u : 0u;
+  for (int e = 0; e < 8; e++) {
+    const int bit = 8 * k + e;
+    if (bit >= 67 && bit < 94 && ((ts_rate >> (26 - (bit - 67))) & 1)) v |= 1u << (7 - e);
+  }
+  return v;
+}
 
-// GOUT (the chain's BB pass): the BBFRAME words go straight to the block's codeword row outw, not through
-// the LDS frame and a copy (fec 1.553 -> 1.539 ms per 1280 cfg3 frames)
-template <bool CRC_RESIDENT, bool PRE, bool GOUT = false>
+// The block kernel's BBFRAME (fec_kernel<FEC_TS_TO_BITS>): FEC block B (absolute index) into frame[0, L) in LDS.
+// NM: the CRC-8 tables are loaded (per block: the LDPC mode's areas overlay them), the raw stream bytes staged
+// once, and each sync slot's CRC-8 computed by 8 lanes; then BBHEADER + its CRC-8, the payload words, the in-band
+// field, BB scrambling with d.prbs from global memory.  Ends with a barrier.
 __device__ void fec_bbframe(const FecDev &d, const FecIO &io, const FecCarve &cv, unsigned char *smem, int64_t B,
-                            const uint8_t *tin, int tid, const uint4 *pre = nullptr, const BbGeom *gp = nullptr,
-                            uint32_t *outw = nullptr) {
+                            const uint8_t *tin, int tid) {
   const int lane = tid & 63, wave = tid >> 6;
   const int L = d.kbch >> 3;
   uint8_t *frame = smem + cv.frame, *phase = smem + cv.phase;
   uint8_t *crc8 = smem + cv.crc8, *crcsh = smem + cv.crcsh;
-  const uint8_t *crcsl = smem + cv.crcsl;   // BB pass (CRC_RESIDENT): T^1 | T^2 | .. | T^24
   const uint8_t *hcrc8 = smem + cv.hcrc;
   uint8_t *syncv = smem + cv.sync;
-  const BbGeom g = gp ? *gp : bb_geom(d, io, B);
+  const BbGeom g = bb_geom(d, io, B);
   const int npay = g.npay, padding = g.padding, count0 = g.count0;
   const int64_t J0 = g.J0, pos0 = g.pos0;
-  // NM: stage the raw stream bytes once (PRE: the units this thread prefetched, unit tid + 256 k in
-  // pre[k]); the CRC-8 chains and the payload words then read LDS
+  // NM: stage the raw stream bytes once; the CRC-8 chains and the payload words then read LDS
   const int64_t rs = pos0 - 188;
   int delta = 0, first_slot = 0;
   const uint32_t *raww = (const uint32_t *)phase;
   if (!d.hem) {
-    if (!CRC_RESIDENT) {
-      for (int i = tid; i < 64; i += FEC_THREADS) ((uint32_t *)crc8)[i] = ((const uint32_t *)d.crc8_tab)[i];
-      for (int i = tid; i < 512; i += FEC_THREADS) ((uint32_t *)crcsh)[i] = ((const uint32_t *)d.crc8_shift)[i];
-    }
+    for (int i = tid; i < 64; i += FEC_THREADS) ((uint32_t *)crc8)[i] = ((const uint32_t *)d.crc8_tab)[i];
+    for (int i = tid; i < 512; i += FEC_THREADS) ((uint32_t *)crcsh)[i] = ((const uint32_t *)d.crc8_shift)[i];
     delta = g.delta;
     uint4 *rawq = (uint4 *)phase;
-    if (PRE) {
-#pragma unroll
-      for (int k = 0; k < FEC_PRE; k++)
-        if (tid + FEC_THREADS * k < g.nq) rawq[tid + FEC_THREADS * k] = pre[k];
-    } else {
-      for (int i = tid; i < g.nq; i += FEC_THREADS) rawq[i] = bb_raw_unit(io, tin, g.w0, i);
-    }
+    for (int i = tid; i < g.nq; i += FEC_THREADS) rawq[i] = bb_raw_unit(io, tin, g.w0, i);
     const uint8_t *raw = phase + delta;
     __syncthreads();
     first_slot = (188 - count0) % 188;
@@ -500,46 +491,13 @@ __device__ void fec_bbframe(const FecDev &d, const FecIO &io, const FecCarve &cv
       if (active) {
         const int n = k == 7 ? 19 : 24;            // 187 = 7 x 24 + 19
         uint32_t c = 0;
-        if (CRC_RESIDENT) {
-          // T is linear, so the register after bytes b_0 .. b_23 from c = 0 is the XOR of T^(24 - i)[b_i]:
-          // 24 independent lookups (the BB pass keeps T^1 .. T^24 in LDS) instead of a chain of dependent
-          // ones (slicing by 4 had six LDS round trips in a row: the CRC phase was ~0.18 ms of the pass);
-          // the 19-byte last chunk is front-padded with zero bytes, T^k[0] = 0
-          // the chunk's bytes as six aligned dwords (seven dword reads and a byte align each) instead of
-          // 24 byte reads
-          const int pad = 24 - n;
-          const uint8_t *bp = raw + (p - 187 + 24 * k - rs) - pad;
-          const uint32_t sh = (uint32_t)((uintptr_t)bp & 3u);
-          const uint32_t *bw = (const uint32_t *)(bp - sh);
-          uint32_t w7[7], t[24];
+        const uint8_t *b0 = raw + (p - 187 + 24 * k - rs);
+        uint8_t by[24];
 #pragma unroll
-          for (int j = 0; j < 7; j++) w7[j] = bw[j];
+        for (int i = 0; i < 24; i++) by[i] = i < n ? b0[i] : 0;
 #pragma unroll
-          for (int j = 0; j < 6; j++) {
-            const uint32_t a = __builtin_amdgcn_alignbyte(w7[j + 1], w7[j], sh);
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-              const int i = 4 * j + e;
-              uint32_t by = (a >> (8 * e)) & 0xFFu;
-              if (i < 5) by = i >= pad ? by : 0u;   // pad is 0 or 5
-              t[i] = crcsl[(23 - i) * 256 + by];
-            }
-          }
-          // all 24 lookups in flight, then an XOR tree (a running XOR had the compiler wait per pair)
-#pragma unroll
-          for (int h = 12; h >= 3; h >>= 1)
-#pragma unroll
-            for (int i = 0; i < h; i++) t[i] ^= t[i + h];
-          c = t[0] ^ t[1] ^ t[2];
-        } else {
-          const uint8_t *b0 = raw + (p - 187 + 24 * k - rs);
-          uint8_t by[24];
-#pragma unroll
-          for (int i = 0; i < 24; i++) by[i] = i < n ? b0[i] : 0;
-#pragma unroll
-          for (int i = 0; i < 24; i++)
-            if (i < n) c = crc8[by[i] ^ c];
-        }
+        for (int i = 0; i < 24; i++)
+          if (i < n) c = crc8[by[i] ^ c];
         part = crcsh[k * 256 + c];
       }
       // XOR of the 8 lanes' parts into lane k == 0: DPP quad_perm [1,0,3,2], [2,3,0,1], row_shl:4
@@ -564,6 +522,7 @@ __device__ void fec_bbframe(const FecDev &d, const FecIO &io, const FecCarve &cv
   }
   // BBHEADER (bbheader:272-325), uniform across the workgroup: MATYPE (FecDev::matype: TS, SIS or MIS
   // with ISI, CCM, ISSYI 0, NPD 0, RO 0); bytes 0..7 big-endian in hw, byte 8 = SYNCD low, byte 9 = CRC-8
+  // (bbch_kernel builds the same word in its chunk-0 lanes)
   const uint32_t upl = d.hem ? 0u : 188u * 8u, dfl = (uint32_t)(d.kbch - 80 - padding);
   const uint32_t syncb = d.hem ? 0u : 0x47u, syncd = count0 == 0 ? 0u : (uint32_t)(188 - count0) * 8u;
   const uint64_t hw = ((uint64_t)(uint32_t)d.matype << 48) | ((uint64_t)upl << 32) | ((uint64_t)dfl << 16) | ((uint64_t)syncb << 8) |
@@ -589,21 +548,14 @@ __device__ void fec_bbframe(const FecDev &d, const FecIO &io, const FecCarve &cv
       const int r = (count0 + j) % 188;
       return r == 0 ? (uint32_t)syncv[(j - first_slot) / 188] : (uint32_t)phase[delta + 188 + j];
     }
-    const int k = j - npay;   // in-band type B (bbheader:327-355): 01, 65 zero bits, TS rate (27 bits), 10 zeros
+    const int k = j - npay;   // the in-band type B field after the payload
     if (!padding || k >= 13) return 0u;
-    uint32_t v = k == 0 ? 0x40u : 0u;
-    for (int e = 0; e < 8; e++) {
-      const int bit = 8 * k + e;
-      if (bit >= 67 && bit < 94 && ((d.ts_rate >> (26 - (bit - 67))) & 1)) v |= 1u << (7 - e);
-    }
-    return v;
+    return inband_byte(k, d.ts_rate);
   };
   // BBFRAME words = header | payload (each sync slot carries the CRC-8 of the previous packet,
   // bbheader:701-719) | in-band field, BB-scrambled (:694-696, :724-726)
-  uint32_t *framew = GOUT ? outw : (uint32_t *)frame;
-  // (the BB pass keeps the PRBS in LDS: a global load per word here was waited for with vmcnt(0),
-  // which also waited for the next block's prefetched TS units)
-  const uint32_t *prbsw = CRC_RESIDENT ? (const uint32_t *)(smem + cv.prbs) : (const uint32_t *)d.prbs;
+  uint32_t *framew = (uint32_t *)frame;
+  const uint32_t *prbsw = (const uint32_t *)d.prbs;
   // bulk payload words (NM: bytes 10 + j, j in [0, npay), whole words w in [3, wf1)) from the staged
   // stream; the few others (header, the edges, in-band field; every word in HEM) in a separate loop,
   // so the bulk loop carries no global loads or their waits
@@ -664,7 +616,7 @@ __global__ __launch_bounds__(FEC_THREADS, FEC_WG_PER_CU) void fec_kernel(FecDev 
     if (MODE == FEC_TS_TO_BITS) {
       const uint8_t *tin;
       const int64_t B = fec_block_of(io, bi, tin);
-      fec_bbframe<false, false>(d, io, cv, smem, B, tin, tid);
+      fec_bbframe(d, io, cv, smem, B, tin, tid);
       // BCH on wave 0 (raised issue priority: the block's critical path)
       if (wave == 0) {
         __builtin_amdgcn_s_setprio(1);
@@ -711,13 +663,8 @@ __global__ __launch_bounds__(FEC_THREADS, FEC_WG_PER_CU) void fec_kernel(FecDev 
   }
 }
 
-// ---- chain pass 2: BCH as a GF(2) matrix product on the matrix cores
-typedef int bch_v8i __attribute__((ext_vector_type(8)));
-typedef float bch_v16f __attribute__((ext_vector_type(16)));
-
-// ---- chain FEC, fused (round 6): the BB pass and the matrix-core BCH as one kernel, bbch_kernel
-// The BB pass wrote each BBFRAME to HBM and the BCH pass read it back (1.7 x the FEC stage's minimal bytes).
-// Here each lane builds its own A-fragment piece -- BBFRAME bytes [P0, P0 + 16), P0 = 32 q + 16 h, of its block
+// ---- chain FEC: the BBFRAMEs and the BCH as a GF(2) matrix product on the matrix cores in one kernel, bbch_kernel
+// Each lane builds its own A-fragment piece -- BBFRAME bytes [P0, P0 + 16), P0 = 32 q + 16 h, of its block
 // (h = lane >> 5) -- straight from the TS in registers: the payload bytes of the stream with each sync slot
 // replaced by the CRC-8 of the packet before it (bbheader:701-719; HEM: the sync bytes dropped, :673-680), the
 // BBHEADER in chunk 0 (:272-325), the in-band type B field after the payload (:327-355), BB scrambling
@@ -730,6 +677,8 @@ typedef float bch_v16f __attribute__((ext_vector_type(16)));
 // register to each other once per piece.  A tile segment starting at chunk q0 first streams the CRC through the
 // BBCH_PRO chunks (192 stream bytes) before it, so a sync position (one every 188 bytes) has restarted the
 // register before the first slot it fills.
+typedef int bch_v8i __attribute__((ext_vector_type(8)));       // the fp4 MFMA's A / B operand
+typedef float bch_v16f __attribute__((ext_vector_type(16)));   // and its 32 x 32 accumulator
 constexpr int BBCH_THREADS = 256;   // 4 waves: a tile of 128 FEC blocks per workgroup, two workgroups per CU (up
 constexpr int BBCH_ROWS = 128;      // to 256 VGPRs: two waves per SIMD)
 constexpr int BBCH_WG_PER_CU = 2;
@@ -898,7 +847,7 @@ __global__ __launch_bounds__(BBCH_THREADS, BBCH_WG_PER_CU) void bbch_kernel(FecD
     const int e = tid >> 2, k = tid & 3, n = min(max(e + 1 - 4 * k, 0), 4);
     ((uint32_t *)pmask)[tid] = n >= 4 ? 0xFFFFFFFFu : (1u << (8 * n)) - 1u;
   }
-  if (tid < 13) {
+  if (tid < 13) {   // = inband_byte(tid, d.ts_rate), written out: calling it here changes this kernel's code
     uint32_t v = tid == 0 ? 0x40u : 0u;
     for (int e = 0; e < 8; e++) {
       const int bit = 8 * tid + e;
@@ -917,7 +866,7 @@ __global__ __launch_bounds__(BBCH_THREADS, BBCH_WG_PER_CU) void bbch_kernel(FecD
   const int64_t u1 = units * (kq + 1) / per_slice;
   // chunk q's B fragments (t2_plan build_bch_mfma, lane-linear): loaded into registers a chunk ahead, written to
   // LDS buffer buf after the chunk's MFMAs.  Not LDS-DMA: the compiler cannot tell which LDS bytes a DMA writes,
-  // so it waits for every outstanding DMA with vmcnt(0) before any LDS read.  (In round 5's bch_gemm_kernel that
+  // so it waits for every outstanding DMA with vmcnt(0) before any LDS read.  (In round 5's separate BCH kernel that
   // wait sat right after the next chunk's DMA, so its double buffer never overlapped a DMA with the MFMAs; here
   // vmcnt(0) would also drain the BBFRAME stores.)
   // (a vector value, not a uint4 array: the array was kept in scratch memory, a store and a reload per chunk)
@@ -1204,10 +1153,10 @@ __global__ __launch_bounds__(BBCH_THREADS, BBCH_WG_PER_CU) void bbch_kernel(FecD
   }
 }
 
-// chain pass 3: info bytes [0, L) from the codeword row + the BCH parity (the XOR of the K slices),
-// the info groups laid out, LDPC, then the interleaver-input words from word L / 4 on (the BB pass
-// wrote the words before): BCH parity | LDPC parity (parity interleaved: byte m = byte m % 45 of row
-// m / 45, or natural order a + q c for QPSK without parity interleaving)
+// ---- the chain's LDPC stage (ldpc_map_kernel, below): info bytes [0, L) from the codeword row (bbch_kernel
+// stored the BBFRAME there) + the BCH parity (the XOR of the K slices), the info groups laid out, LDPC, then
+// the interleaver-input words: BBFRAME | BCH parity | LDPC parity (parity interleaved: byte m = byte m % 45 of
+// row m / 45, or natural order a + q c for QPSK without parity interleaving)
 // word i (bytes 4 i .. 4 i + 3, little-endian as stored) of block's interleaver-input codeword: the
 // BBFRAME and BCH parity bytes from frame, then the LDPC parity rows cur (fec_ldpc), parity-interleaved
 // (byte m = byte m mod 45 of row m / 45) by byte-aligning two row words where the code has the parity
@@ -1264,9 +1213,10 @@ static int fec_grid(int nblocks, int per_cu) {
 }
 
 static bool fec_plan_fits(const FecDev &d) {
-  // the LDS carve is sized for the standard codes, the BCH wave for 64 chunks: refuse anything else
+  // the LDS carve is sized for the standard codes, the BCH wave for 64 chunks, ldpc_map_kernel's row load for
+  // LM_ROW_UNITS units per thread: refuse anything else
   return !(d.nent > FEC_MAX_ENT || d.q > 128 || d.nbch > 8 * FEC_FRAME_BYTES || 4 * FEC_DW_PASS * (d.nbch / 360) + 48 * d.q > FEC_LDPC_BYTES ||
-           (d.kbch - 80) / 8 + 218 > 16 * FEC_PRE * FEC_THREADS || ((d.kbch >> 3) + 15) / 16 > FEC_PRE * FEC_THREADS ||
+           ((d.kbch >> 3) + 15) / 16 > LM_ROW_UNITS * FEC_THREADS ||
            (d.P != 192 && d.P != 168 && d.P != 160 && d.P != 128) || d.chunk * 64 < d.kbch / 8);
 }
 
@@ -1726,7 +1676,7 @@ hipError_t launch_map(const MapDev &d, const MapIO &io, hipStream_t s) {
 // ============================================================================ chain: LDPC + map
 // One 256-thread workgroup per FEC block of the launch (after ceil8(L1 frames) workgroups that generate
 // the frames' L1-post cells): the block's BBFRAME and the XOR of its BCH partial
-// parities (the BB and matrix-core passes' output) -> LDPC parity (fec_ldpc) -> the interleaver-input
+// parities (bbch_kernel's output) -> LDPC parity (fec_ldpc) -> the interleaver-input
 // codeword, built in LDS -> column twist + demux (map_cells) -> cell interleaver + time-interleaver
 // store of the index pairs (map_store_quads).  The codeword never goes through HBM (the LDPC stage's
 // 8 KB store and the map stage's 8 KB load per normal block); fio.keep_cw (test hook) stores it anyway.
@@ -1740,8 +1690,8 @@ __host__ __device__ inline int lm_smem(const FecDev &fd, int cs) {
 }
 static_assert(FEC_THREADS == MAP_THREADS, "ldpc_map_kernel runs the map phases at FEC_THREADS");
 
-__global__ __launch_bounds__(FEC_THREADS, FEC_PASS_WG_PER_CU) void ldpc_map_kernel(FecDev fd, FecIO fio, MapDev md,
-                                                                                   MapIO mio, L1Dev l1d, L1IO l1io) {
+__global__ __launch_bounds__(FEC_THREADS, LM_WG_PER_CU) void ldpc_map_kernel(FecDev fd, FecIO fio, MapDev md, MapIO mio,
+                                                                             L1Dev l1d, L1IO l1io) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int nl1 = (l1io.nframes + 7) & ~7;
@@ -1762,9 +1712,9 @@ __global__ __launch_bounds__(FEC_THREADS, FEC_PASS_WG_PER_CU) void ldpc_map_kern
   {
     // the BBFRAME's 16-byte units and the BCH partial parity requested before the tables are staged
     const uint4 *rowq = (const uint4 *)row;
-    uint4 u[FEC_PRE];
+    uint4 u[LM_ROW_UNITS];
 #pragma unroll
-    for (int k = 0; k < FEC_PRE; k++)
+    for (int k = 0; k < LM_ROW_UNITS; k++)
       u[k] = tid + FEC_THREADS * k < nqi ? rowq[tid + FEC_THREADS * k] : make_uint4(0u, 0u, 0u, 0u);
     const uint32_t par = tid < (PB + 3) >> 2 ? fio.bch_part[(int64_t)blk * BCH_PART_WORDS + tid] : 0u;
     // consumed: zero the words for the next run on this buffer slot (bbch_kernel XOR-accumulates into them)
@@ -1772,7 +1722,7 @@ __global__ __launch_bounds__(FEC_THREADS, FEC_PASS_WG_PER_CU) void ldpc_map_kern
     for (int i = tid; i < fd.nent; i += FEC_THREADS) ents[i] = fd.ldpc_ent[i];
     for (int i = tid; i <= q; i += FEC_THREADS) rowp[i] = fd.ldpc_rowptr[i];
 #pragma unroll
-    for (int k = 0; k < FEC_PRE; k++)
+    for (int k = 0; k < LM_ROW_UNITS; k++)
       if (tid + FEC_THREADS * k < nqi) ((uint4 *)frame)[tid + FEC_THREADS * k] = u[k];
     __syncthreads();   // the 16-byte units past L land before the parity bytes overwrite them
     if (tid < (PB + 3) >> 2)
@@ -1794,7 +1744,7 @@ __global__ __launch_bounds__(FEC_THREADS, FEC_PASS_WG_PER_CU) void ldpc_map_kern
     const int i = tid + FEC_THREADS * k;
     w[k] = i < nw ? ldpc_out_word(fd, frame, cur, Wv, i) : 0u;
   }
-  if (fio.keep_cw) {   // test hook: the row as the three-pass FEC stored it (words below L / 4 hold the BBFRAME)
+  if (fio.keep_cw) {   // test hook: the interleaver-input codeword after the BBFRAME already in the row
     uint32_t *dstw = (uint32_t *)row;
 #pragma unroll
     for (int k = 0; k < LM_WORDS; k++) {

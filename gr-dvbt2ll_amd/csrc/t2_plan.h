@@ -33,7 +33,7 @@ struct FecPlan {
   // per-lane chunk shift as nibble tables: entry [j][v][lane] (4 words, the 4th zero) =
   // v x^(4 j) x^(8 chunk (63 - lane)) mod g for nibble j < P/4, value v < 16, lane < 64
   std::vector<uint64_t> bch_ctab;
-  // the chain's BCH as a GF(2) matrix product on the matrix cores (bch_gemm_kernel): fp4 B
+  // the chain's BCH as a GF(2) matrix product on the matrix cores (bbch_kernel): fp4 B
   // fragments [32-byte message chunk q < bch_nq][K-step u < 4][parity tile t < bch_nt][lane][4
   // dwords] of the parity-generator matrix (layout: build_bch_mfma)
   int bch_nq = 0, bch_nt = 0;

@@ -141,7 +141,8 @@ def bch_mfma_table(framesize, rate):
 
 def ti_dest(plan, r, t):
     """frame data-region index of cell t (cell-interleaved position) of FEC block r: the
-    time-interleaver write the chain's map kernel performs (t2_kernels.hip map_kernel)"""
+    time-interleaver write of the map stage (t2_kernels.hip map_store_quads: the block API's map_kernel
+    and the chain's ldpc_map_kernel)"""
     cs = plan["cs"]
     if not plan["ti_on"]:
         return r * cs + t

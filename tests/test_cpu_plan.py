@@ -308,7 +308,7 @@ def _gf2_mod(v, g):
 
 @pytest.mark.parametrize("framesize,rate", [(1, r) for r in range(6)] + [(0, r) for r in range(8)])
 def test_bch_lane_shift_tables(framesize, rate):
-    """The FEC kernel's BCH (t2_kernels.hip bch_wave_part, FEC_BCH_TAB): 64 lanes divide
+    """The block-API FEC kernel's BCH (t2_kernels.hip bch_wave, tables bch_tab / bch_ctab): 64 lanes divide
     consecutive chunks of the BBFRAME by the byte table, then each lane moves its remainder to
     the end of the message with P/4 nibble-table lookups and the lanes' results are XORed.  That
     must equal the byte-table division of the whole message, and message || parity must be a

@@ -345,8 +345,8 @@ CW_CASES = [(m, i, E.MOD_16QAM) for m, i in MODES] + [(E.INPUTMODE_NORMAL, E.INB
 @pytest.mark.parametrize("framesize,rate", ALL_CODES)
 @pytest.mark.parametrize("mode,inband,const", CW_CASES, ids=["nm", "hem", "nm-inband", "nm-qpsk"])
 def test_chain_codewords_all_codes(gpu, framesize, rate, mode, inband, const):
-    """the chain's FEC passes (BB pass, BCH on the matrix cores, LDPC pass) for every code x input
-    mode: the packed interleaver-input codewords of two frames equal the oracle's bbheaderbch + ldpc
+    """the chain's FEC kernels (bbch_kernel: BBFRAMEs + BCH on the matrix cores; ldpc_map_kernel's LDPC
+    stage) for every code x input mode: the packed interleaver-input codewords of two frames equal the oracle's bbheaderbch + ldpc
     output (info bits, then the parity interleaved [row a][column c] where the constellation has it)"""
     import plan_probe as PP
     cfg = CONFIGS["cfg4"].with_(framesize=framesize, rate=rate, inputmode=mode, inband=inband, constellation=const,
