@@ -1326,6 +1326,8 @@ static int chain_run(dvbt2ll_chain *h, const void *const *ts, const int64_t *bas
   if (!h || !ts || !iq_dev || nframes < 1 || nstreams < 1 || (int64_t)nframes * nstreams > h->max_frames ||
       first_frame < 0 || (nstreams > 1 && (h->nplp > 1 || ts_stride < len[0])))
     return DVBT2LL_EINVAL;
+  // iq_dev is aligned to one output sample (the IQ stores are whole samples, or pairs where the address allows)
+  if ((uintptr_t)iq_dev % (h->ofdm.dev.fmt == DVBT2LL_IQ_SC16 ? 4u : 8u)) return DVBT2LL_EINVAL;
   // whole interleaving frames of every PLP (TIME_IL_TYPE 1: P_I T2 frames each)
   if (first_frame % h->frame.unit || nframes % h->frame.unit) return DVBT2LL_EINVAL;
   const int nf = nframes * nstreams;   // frames of the launch, stream-major

@@ -170,8 +170,11 @@ int dvbt2ll_chain_get_info(const dvbt2ll_chain *h, dvbt2ll_chain_info *info);
  * (a multiple of 188, else DVBT2LL_EINVAL; at least one packet before the first byte the frames consume so
  * the CRC-8 of the preceding packet can be formed); ts_len bytes valid.  iq_dev receives
  * nframes * iq_samples_per_frame samples (complex64, or int16 I/Q pairs after
- * dvbt2ll_chain_set_output(.., DVBT2LL_IQ_SC16)).  stream: hipStream_t (NULL = the handle's
- * own stream).  Asynchronous on that stream. */
+ * dvbt2ll_chain_set_output(.., DVBT2LL_IQ_SC16)).  iq_dev must be aligned to one output sample:
+ * 8 bytes for DVBT2LL_IQ_CF32, 4 bytes for DVBT2LL_IQ_SC16 (else DVBT2LL_EINVAL, nothing is launched).
+ * Any such address is valid, e.g. an odd sample offset into a larger buffer (the kernels store sample
+ * pairs where the address allows and single samples elsewhere, the same bits either way).  stream:
+ * hipStream_t (NULL = the handle's own stream).  Asynchronous on that stream. */
 int dvbt2ll_chain_run_device(dvbt2ll_chain *h, const void *ts_dev, int64_t ts_base, int64_t ts_len,
                              int64_t first_frame, int nframes, void *iq_dev, void *stream);
 /* multi-stream batch (BASELINE cfg4 "4 independent PLP streams", cfg5 "8-stream batch"): nstreams
@@ -180,7 +183,8 @@ int dvbt2ll_chain_run_device(dvbt2ll_chain *h, const void *ts_dev, int64_t ts_ba
  * the three kernels.  Stream s's TS bytes are at ts_dev + s * ts_stride, every stream laid out as
  * run_device's ts_dev (the same ts_base and ts_len; ts_stride >= ts_len); all streams encode frames
  * [first_frame, first_frame + nframes).  IQ: stream s, frame first_frame + j at sample
- * (s * nframes + j) * iq_samples_per_frame of iq_dev.  nstreams * nframes <= max_frames.
+ * (s * nframes + j) * iq_samples_per_frame of iq_dev (aligned to one output sample, as run_device's).
+ * nstreams * nframes <= max_frames.
  * run_device(...) == run_streams(h, ts, 0, 1, ...).  Asynchronous on stream. */
 int dvbt2ll_chain_run_streams(dvbt2ll_chain *h, const void *ts_dev, int64_t ts_stride, int nstreams,
                               int64_t ts_base, int64_t ts_len, int64_t first_frame, int nframes,
@@ -346,7 +350,8 @@ int dvbt2ll_chain_unit_frames(const dvbt2ll_chain *h);
  * codeword stride; the frame-wide fields as dvbt2ll_chain_get_info (which reports PLP 0's) */
 int dvbt2ll_chain_get_plp_info(const dvbt2ll_chain *h, int plp, dvbt2ll_chain_info *info);
 /* ts_dev[k], ts_base[k], ts_len[k]: PLP k's TS, laid out as run_device's (host arrays of nplp entries);
- * frames [first_frame, first_frame + nframes) into iq_dev.  Asynchronous on stream.  run_device on a
+ * frames [first_frame, first_frame + nframes) into iq_dev (aligned to one output sample, as
+ * run_device's: 8 bytes for DVBT2LL_IQ_CF32, 4 for DVBT2LL_IQ_SC16).  Asynchronous on stream.  run_device on a
  * one-PLP chain == run_plps with one entry. */
 int dvbt2ll_chain_run_plps(dvbt2ll_chain *h, const void *const *ts_dev, const int64_t *ts_base,
                            const int64_t *ts_len, int64_t first_frame, int nframes, void *iq_dev, void *stream);
