@@ -76,6 +76,7 @@ void usage(FILE *f) {
                "                          pilotpattern t2frames numdatasyms paprmode version preamble\n"
                "                          inputmode reservedbiasbits l1scrambled inband; pilotgen:\n"
                "                          misogroup equalization bandwidth; bbheaderbch: tsrate)\n"
+               "                          misogroup: 0 TX1, 1 TX2 (pilots only), 2 TX2 with MISO processing\n"
                "  --format cf32|sc16      IQ sample format (default cf32, pilotgen's complex64)\n"
                "  --gain G                output gain (the flowgraph's multiply_const; default 1)\n"
                "  --frames N              T2 frames to encode (default: as many as the input holds)\n"

@@ -601,6 +601,7 @@ struct OfdmTables {
     dev.p1 = p1.as<float2>();
     dev.N = pp.N; dev.G = pp.G; dev.Nsym = pp.Nsym; dev.aux_len = aux_len; dev.t2frames = t2frames;
     dev.norm = pp.normalization;
+    dev.miso = pp.miso_proc;
     dev.gain = 1.f;
     dev.fmt = DVBT2LL_IQ_CF32;
     return 0;
@@ -1142,8 +1143,10 @@ static int chain_build(dvbt2ll_chain *h, const FmParams &fm, const std::vector<P
   std::vector<int32_t> cls_inv, sd0, sdn, sdn0, bnd_all;
   for (const ChainLayout &lc : layouts) {
     cls_inv.push_back((int32_t)inv_pad.size());
+    // (MISO-processed frames: the selector stays in the padded bin's top bit)
+    const uint16_t selbit = h->pilot.miso_proc ? (uint16_t)(1u << MISO_INV_SEL_BIT) : (uint16_t)0;
     for (size_t si = 0; si < lc.inv.size(); si++)
-      inv_pad.push_back((uint16_t)ofdm_padded_bin(h->pilot.N, lc.inv[si] % nsub_h));
+      inv_pad.push_back((uint16_t)(ofdm_padded_bin(h->pilot.N, (lc.inv[si] & ~selbit) % nsub_h) | (lc.inv[si] & selbit)));
     inv_pad.resize(((inv_pad.size() + 7) & ~(size_t)7) + 8, 0);
     sd0.insert(sd0.end(), lc.sym_d0.begin(), lc.sym_d0.end());
     sdn.insert(sdn.end(), lc.sym_n.begin(), lc.sym_n.end());
@@ -1178,7 +1181,7 @@ static int chain_build(dvbt2ll_chain *h, const FmParams &fm, const std::vector<P
   h->l1_stride = (uint32_t)((fp.Lp + 3) & ~3);
   for (auto &b : al.dbin)
     if (b != 0xFFFF) b = (uint16_t)ofdm_padded_bin(pp.N, b);
-  for (auto &e : al.ind) e = ofdm_padded_bin(pp.N, e & 0x7FFFu) | (e & ~0x7FFFu);
+  for (auto &e : al.ind) e = ofdm_padded_bin(pp.N, e & 0x7FFFu) | (e & ~0x7FFFu);   // (code and selector bits kept)
   std::vector<int32_t> zr(al.zrun.size());   // zero runs as padded slot ranges
   for (size_t g = 0; g + 1 < al.zrun.size(); g += 2) {
     const int z0 = al.zrun[g], z1 = al.zrun[g + 1];

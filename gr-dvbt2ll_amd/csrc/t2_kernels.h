@@ -156,6 +156,11 @@ struct OfdmDev {
   float norm;
   float gain;               // output gain after the normalisation (1 = pilotgen's own output)
   int fmt;                  // IQ format: 0 complex64, 1 int16 I/Q (sc16, full scale 32767)
+  // MISO-processed payload (t2_plan.h MISO_TX2_PROCESSED; selects the kernels' MISO instantiation): the data
+  // codes of bin_map (gather mode), the bins of inv and the entries of aind carry a one-bit selector (bits 30,
+  // 15 and 31; aind's codes are then 16 bits), and the cell read through them is stored with one sign bit
+  // flipped: selector 0 (x, -y), selector 1 (-x, y).  The direct aux values are flipped on the host.
+  int miso;
 };
 struct OfdmIO {
   const float2 *data;       // gather mode: aux variants at aux_off, frame f cells at cell_off + f*cell_stride

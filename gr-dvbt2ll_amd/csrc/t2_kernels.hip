@@ -2022,14 +2022,21 @@ struct NoWork {
 };
 // mid (32K): register work independent of the LDS, run once by every thread while its first round
 // of data-slot loads is in flight (after the loop when the run has no slots)
-template <int NT, int SQ, class Mid>
+template <int NT, int SQ, bool MISO, class Mid>
 __device__ __forceinline__ void scatter_slots(float2 *lds, const BinSource &src, uint32_t r0, uint32_t rn,
                                               uint32_t dummy, int tid, const Mid &mid, uint32_t lb,
                                               const SlotPre *pre = nullptr);
+// MISO (kernel instantiations of their own, as MULTI's): MISO-processed payload (OfdmDev::miso).  The cell a
+// bin table entry names is the carrier's partner, stored with one sign bit flipped by the entry's one-bit
+// selector sel: (x, -y) for 0 (conj), (-x, y) for 1 (-conj); two XORs on registers
+__device__ __forceinline__ float2 miso_flip(float2 v, uint32_t sel) {
+  const uint32_t sx = sel << 31;
+  return make_float2(__uint_as_float(__float_as_uint(v.x) ^ sx), __uint_as_float(__float_as_uint(v.y) ^ sx ^ 0x80000000u));
+}
 // MULTI (a kernel instantiation of its own, so the one-PLP kernels keep their register allocation):
 // the data slots of a multi-PLP frame, streamed PLP by PLP (a group's slots are PLP-major), each
 // PLP's run looked up in its own constellation table
-template <int NT, int SQ, bool MULTI = false, class Mid = NoWork>
+template <int NT, int SQ, bool MULTI = false, bool MISO = false, class Mid = NoWork>
 __device__ __forceinline__ void scatter_group(float2 *lds, const BinSource &src, int g, uint32_t r0, uint32_t rn,
                                               uint32_t dummy, int tid, const Mid &mid = Mid(),
                                               const SlotPre *pre = nullptr) {
@@ -2068,23 +2075,27 @@ __device__ __forceinline__ void scatter_group(float2 *lds, const BinSource &src,
   }
   for (uint32_t i = (uint32_t)tid; i < (uint32_t)gr.w; i += NT) {
     const uint32_t e = src.aind[(uint32_t)gr.z + i];
-    lds[e & 0x7FFFu] = ld_off(src.data, (src.abase + (e >> 15)) * 8u);
+    if (MISO)   // 16-bit code, the selector above it
+      lds[e & 0x7FFFu] = miso_flip(ld_off(src.data, (src.abase + ((e >> 15) & 0xFFFFu)) * 8u), e >> 31);
+    else
+      lds[e & 0x7FFFu] = ld_off(src.data, (src.abase + (e >> 15)) * 8u);
   }
   if (MULTI) {
     mid();
     const int P = src.nplp;
     for (int p = 0; p < P; p++) {   // (uniform)
       const uint32_t a = (uint32_t)kc(src.bnd, g * (P + 1) + p), b = (uint32_t)kc(src.bnd, g * (P + 1) + p + 1);
-      if (b > a) scatter_slots<NT, SQ>(lds, src, a, b - a, dummy, tid, NoWork(), (uint32_t)kc(src.qbase, p));
+      if (b > a) scatter_slots<NT, SQ, MISO>(lds, src, a, b - a, dummy, tid, NoWork(), (uint32_t)kc(src.qbase, p));
     }
   } else {
-    scatter_slots<NT, SQ>(lds, src, r0, rn, dummy, tid, mid, 0u, pre);
+    scatter_slots<NT, SQ, MISO>(lds, src, r0, rn, dummy, tid, mid, 0u, pre);
   }
 }
 
 // the data slots [r0, r0 + rn): streamed as aligned octets (32K) or quads, looked up in the constellation
-// table at lb of qre / qim (QAM + rotated-Q delay) and written to their bins
-template <int NT, int SQ, class Mid>
+// table at lb of qre / qim (QAM + rotated-Q delay) and written to their bins (MISO: bin bit 15 is the
+// selector of the sign flip, applied in registers between the lookups and the writes)
+template <int NT, int SQ, bool MISO, class Mid>
 __device__ __forceinline__ void scatter_slots(float2 *lds, const BinSource &src, uint32_t r0, uint32_t rn,
                                               uint32_t dummy, int tid, const Mid &mid, uint32_t lb,
                                               const SlotPre *pre) {
@@ -2122,9 +2133,10 @@ __device__ __forceinline__ void scatter_slots(float2 *lds, const BinSource &src,
 #pragma unroll
         for (int e = 0; e < 8; e++) {
           const uint32_t bw = e < 2 ? b[u].x : e < 4 ? b[u].y : e < 6 ? b[u].z : b[u].w;
-          const uint32_t bin = (bw >> (16 * (e & 1))) & 0xFFFFu;   // padded, within the group
+          const uint32_t bs = (bw >> (16 * (e & 1))) & 0xFFFFu;
+          const uint32_t bin = MISO ? bs & 0x7FFFu : bs;   // padded, within the group
           const bool in_run = s + (uint32_t)e - r0 < rn;
-          lds[in_run ? bin : dummy] = v[e];
+          lds[in_run ? bin : dummy] = MISO ? miso_flip(v[e], bs >> 15) : v[e];
         }
       }
     }
@@ -2164,9 +2176,10 @@ __device__ __forceinline__ void scatter_slots(float2 *lds, const BinSource &src,
         const int uu = u + (e >> 2), ee = e & 3;
         const uint32_t s = q0 + 4u * min(g0 + (uint32_t)(tid + NT * uu), lastq);
         const uint32_t bw = (ee & 2) ? b[uu].y : b[uu].x;
-        const uint32_t bin = (bw >> (16 * (ee & 1))) & 0xFFFFu;   // padded, within the group
+        const uint32_t bs = (bw >> (16 * (ee & 1))) & 0xFFFFu;
+        const uint32_t bin = MISO ? bs & 0x7FFFu : bs;   // padded, within the group
         const bool in_run = s + (uint32_t)ee - r0 < rn;
-        lds[in_run ? bin : dummy] = v[e];
+        lds[in_run ? bin : dummy] = MISO ? miso_flip(v[e], bs >> 15) : v[e];
       }
     }
   }
@@ -2203,7 +2216,7 @@ __device__ __forceinline__ void slot_prefetch(SlotPre &p, const uint16_t *inv, c
 // v[u*RL + r] = y[t + NT*(u + (V/RL)*r)].  Also stores the kernel's constant tables (`stage`) to LDS.
 // pre: the scatter's first round, loaded before (null: loaded here); after_scatter: run once the
 // scatter is in LDS (the next unit's slot_prefetch)
-template <int NSUB, int V, bool MULTI, class Stage, class After = NoWork>
+template <int NSUB, int V, bool MULTI, bool MISO, class Stage, class After = NoWork>
 __device__ __forceinline__ void sub_ifft(float2 *v, float2 *lds, const BinSource &src, const float *isinc,
                                          const float2 *tw, int tid, const Stage &stage, const SlotPre *pre = nullptr,
                                          const After &after_scatter = After(), bool nobar = false) {
@@ -2221,7 +2234,7 @@ __device__ __forceinline__ void sub_ifft(float2 *v, float2 *lds, const BinSource
       lds_barrier();
     }
     const uint32_t dummy = (uint32_t)(NSUB + (NSUB >> PS)) + (uint32_t)(tid & 63);
-    scatter_group<NT, OFDM_SQ16, MULTI>(lds, src, 0, src.d0, src.dn, dummy, tid, NoWork(), pre);
+    scatter_group<NT, OFDM_SQ16, MULTI, MISO>(lds, src, 0, src.d0, src.dn, dummy, tid, NoWork(), pre);
     lds_barrier();
     after_scatter();
     StockhamPass<NSUB, NT, V, 1, PS>::load_lds(v, lds, tid);
@@ -2231,13 +2244,21 @@ __device__ __forceinline__ void sub_ifft(float2 *v, float2 *lds, const BinSource
 #pragma unroll
     for (int c0 = 0; c0 < V; c0 += 8) {
       uint32_t off[8];
+      int cd[8];
 #pragma unroll
       for (int u = 0; u < 8; u++) {
         int code = ld_off(src.map, (uint32_t)(tid + NT * (c0 + u)) * 4u);
+        if (MISO) {   // data codes: partner cell | selector << 30
+          cd[u] = code;
+          if (code >= 0) code &= 0x3FFFFFFF;
+        }
         off[u] = (code >= 0 ? src.cbase + (uint32_t)code : src.abase - (uint32_t)code) * 8u;
       }
 #pragma unroll
-      for (int u = 0; u < 8; u++) v[c0 + u] = ld_off(src.data, off[u]);
+      for (int u = 0; u < 8; u++) {
+        v[c0 + u] = ld_off(src.data, off[u]);
+        if (MISO && cd[u] >= 0) v[c0 + u] = miso_flip(v[c0 + u], (uint32_t)cd[u] >> 30);
+      }
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -2382,7 +2403,7 @@ __device__ __forceinline__ UnitSlots unit_slots(const OfdmDev &d, const OfdmIO &
 
 // pf (one-PLP chain frames): in, this unit's first scatter round (loaded by the previous unit or
 // the kernel); out, unit un's (un < 0: none)
-template <int N, int FMT, bool MULTI>
+template <int N, int FMT, bool MULTI, bool MISO>
 __device__ __forceinline__ void ofdm_unit(const OfdmDev &d, const OfdmIO &io, int u, unsigned char *smem,
                                           const TableStage<N> &tabs, int tid, SlotPre *pf = nullptr, int un = -1) {
   using Sh = OfdmShape<N>;
@@ -2419,7 +2440,8 @@ __device__ __forceinline__ void ofdm_unit(const OfdmDev &d, const OfdmIO &io, in
     float2 *o = io.out + (int64_t)f * io.out_stride + (int64_t)j * N;
     for (int k = tid; k < N; k += NT) {
       const int code = map[k];
-      float2 v = data[code >= 0 ? cbase + (uint32_t)code : abase - (uint32_t)code];
+      float2 v = data[code >= 0 ? cbase + (MISO ? (uint32_t)code & 0x3FFFFFFFu : (uint32_t)code) : abase - (uint32_t)code];
+      if (MISO && code >= 0) v = miso_flip(v, (uint32_t)code >> 30);
       if (d.isinc) {
         const float sc = d.isinc[(k + N / 2) & (N - 1)];
         v.x *= sc;
@@ -2446,9 +2468,9 @@ __device__ __forceinline__ void ofdm_unit(const OfdmDev &d, const OfdmIO &io, in
                           d.aval);
       }
     };
-    sub_ifft<N, V, MULTI>(v, lds, src, d.isinc, twl, tid, tabs, pf, next, true);
+    sub_ifft<N, V, MULTI, MISO>(v, lds, src, d.isinc, twl, tid, tabs, pf, next, true);
   } else {
-    sub_ifft<N, V, MULTI>(v, lds, src, d.isinc, twl, tid, tabs);
+    sub_ifft<N, V, MULTI, MISO>(v, lds, src, d.isinc, twl, tid, tabs);
   }
   if ((((uintptr_t)o.base + (uint32_t)G * SB) & (2u * SB - 1u)) == 0) {
     // two consecutive samples per lane and store: lanes t, t ^ 1 swap half of their values
@@ -2487,7 +2509,7 @@ __device__ __forceinline__ void ofdm_unit(const OfdmDev &d, const OfdmIO &io, in
 // slot bins and aux lists), so the constant tables are loaded once per run and one unit's IQ stores
 // drain while the next unit's bins are loaded.  Runs are XCD-major, so each XCD walks a contiguous
 // range of symbols for all frames of the launch and reads each symbol's tables from its own L2.
-template <int N, int FMT, bool MULTI>
+template <int N, int FMT, bool MULTI, bool MISO>
 __global__ __launch_bounds__(OfdmShape<N>::NT, 4) void ofdm_kernel(OfdmDev d, OfdmIO io) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -2518,9 +2540,9 @@ __global__ __launch_bounds__(OfdmShape<N>::NT, 4) void ofdm_kernel(OfdmDev d, Of
     int t = tid;
     asm volatile("" : "+v"(t));
     if (pre)
-      ofdm_unit<N, FMT, MULTI>(d, io, u, smem, tabs, t, &pf, u + 1 < u1 ? u + 1 : -1);
+      ofdm_unit<N, FMT, MULTI, MISO>(d, io, u, smem, tabs, t, &pf, u + 1 < u1 ? u + 1 : -1);
     else
-      ofdm_unit<N, FMT, MULTI>(d, io, u, smem, tabs, t);
+      ofdm_unit<N, FMT, MULTI, MISO>(d, io, u, smem, tabs, t);
   }
 }
 
@@ -2700,7 +2722,7 @@ __device__ __forceinline__ void o32_store_pairs(const float2 *v, const IqOut<FMT
 
 // 32K symbols, one workgroup per (symbol, frame): scatter mode (the fused chain), gather mode (the
 // pilotgen block: cells already in carrier order) and the carriers-only test hook
-template <int FMT, bool MULTI>
+template <int FMT, bool MULTI, bool MISO>
 __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
   constexpr int N = 32768, NT = O32_NT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2721,7 +2743,8 @@ __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
     float2 *o = io.out + (int64_t)f * io.out_stride + (int64_t)j * N;
     for (int k = tid; k < N; k += NT) {
       const int code = map[k];
-      float2 v = data[code >= 0 ? cbase + (uint32_t)code : abase - (uint32_t)code];
+      float2 v = data[code >= 0 ? cbase + (MISO ? (uint32_t)code & 0x3FFFFFFFu : (uint32_t)code) : abase - (uint32_t)code];
+      if (MISO && code >= 0) v = miso_flip(v, (uint32_t)code >> 30);
       if (d.isinc) {
         const float sc = d.isinc[(k + N / 2) & (N - 1)];
         v.x *= sc;
@@ -2776,7 +2799,7 @@ __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
       tw1k[tid] = t1k;
       if (tid < 384) tw2[tid] = t2;
       lds_barrier();                            // constellation visible to the scatter
-      scatter_group<NT, 4, MULTI>(lds, src, 0, src.d0, src.dn0, dummy, tid);
+      scatter_group<NT, 4, MULTI, MISO>(lds, src, 0, src.d0, src.dn0, dummy, tid);
       lds_barrier();
 #pragma unroll
       for (uint32_t r = 0; r < 16; r++) ev[r] = lds[o32_bin(kin + 1024u * r)];
@@ -2790,7 +2813,7 @@ __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
         __builtin_amdgcn_sched_barrier(0);
         Dft<16>::run(ev);
       };
-      scatter_group<NT, 4, MULTI>(lds, src, 1, src.d0 + src.dn0, src.dn - src.dn0, dummy, tid, dft_even);
+      scatter_group<NT, 4, MULTI, MISO>(lds, src, 1, src.d0 + src.dn0, src.dn - src.dn0, dummy, tid, dft_even);
       lds_barrier();
 #pragma unroll
       for (uint32_t r = 0; r < 16; r++) od[r] = lds[o32_bin(kin + 1024u * r)];
@@ -2805,13 +2828,21 @@ __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
 #pragma unroll
   for (int c0 = 0; c0 < 32; c0 += 8) {
     uint32_t off[8];
+    int cd[8];
 #pragma unroll
     for (int uu = 0; uu < 8; uu++) {
-      const int code = ld_off(map, (kin + 1024u * (uint32_t)(c0 + uu)) * 4u);
+      int code = ld_off(map, (kin + 1024u * (uint32_t)(c0 + uu)) * 4u);
+      if (MISO) {   // data codes: partner cell | selector << 30
+        cd[uu] = code;
+        if (code >= 0) code &= 0x3FFFFFFF;
+      }
       off[uu] = (code >= 0 ? cbase + (uint32_t)code : abase - (uint32_t)code) * 8u;
     }
 #pragma unroll
-    for (int uu = 0; uu < 8; uu++) v[c0 + uu] = ld_off(data, off[uu]);
+    for (int uu = 0; uu < 8; uu++) {
+      v[c0 + uu] = ld_off(data, off[uu]);
+      if (MISO && cd[uu] >= 0) v[c0 + uu] = miso_flip(v[c0 + uu], (uint32_t)cd[uu] >> 30);
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
   eq(v, 32, 1u, 0u);
@@ -2826,32 +2857,34 @@ __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
     o32_store<FMT, 0, 32>(v, o, tb + 32u * ta, d.norm, d.G);
 }
 
-template <int N, int FMT, bool MULTI>
+template <int N, int FMT, bool MULTI, bool MISO>
 static hipError_t launch_ofdm_f(const OfdmDev &d, const OfdmIO &io, hipStream_t s) {
   if (N == 32768) {
-    const void *fn = (const void *)ofdm32_kernel<FMT, MULTI>;
+    const void *fn = (const void *)ofdm32_kernel<FMT, MULTI, MISO>;
     const int lds = o32_lds_bytes(d.inv ? d.nq : 256);
     hipError_t e = lds_limit(fn, o32_lds_bytes(OFDM_MAX_QAM));   // the largest launch
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((ofdm32_kernel<FMT, MULTI>), dim3(d.Nsym * io.nframes), dim3(O32_NT), lds, s, d, io);
+    hipLaunchKernelGGL((ofdm32_kernel<FMT, MULTI, MISO>), dim3(d.Nsym * io.nframes), dim3(O32_NT), lds, s, d, io);
     return hipGetLastError();
   }
   constexpr int NN = N > 16384 ? 16384 : N;
   using Sh = OfdmShape<NN>;
   const int lds = Sh::lds_bytes(d.inv ? d.nq : 256);
-  hipError_t e = lds_limit((const void *)ofdm_kernel<NN, FMT, MULTI>, Sh::lds_bytes(OFDM_MAX_QAM));   // the largest launch
+  hipError_t e = lds_limit((const void *)ofdm_kernel<NN, FMT, MULTI, MISO>, Sh::lds_bytes(OFDM_MAX_QAM));   // the largest launch
   if (e != hipSuccess) return e;
   const int units = d.Nsym * io.nframes;
   // units per workgroup: up to 4 for 8K / 16K, 2 below (cfg4 8K: 2.09 -> 1.81 ms with the slot
   // prefetch; runs of 8 or more leave a grid tail at cfg1's 4K launch sizes, profiles/r5_ofdm_runs.txt),
   // and one per workgroup for small launches (a one-frame call keeps its latency)
   const int run = std::max(1, std::min(NN >= 8192 ? 4 : 2, units / 8192));
-  hipLaunchKernelGGL((ofdm_kernel<NN, FMT, MULTI>), dim3((units + run - 1) / run), dim3(Sh::NT), lds, s, d, io);
+  hipLaunchKernelGGL((ofdm_kernel<NN, FMT, MULTI, MISO>), dim3((units + run - 1) / run), dim3(Sh::NT), lds, s, d, io);
   return hipGetLastError();
 }
 template <int N, int FMT>
 static hipError_t launch_ofdm_m(const OfdmDev &d, const OfdmIO &io, hipStream_t s) {
-  return d.inv && d.nplp > 1 ? launch_ofdm_f<N, FMT, true>(d, io, s) : launch_ofdm_f<N, FMT, false>(d, io, s);
+  const bool multi = d.inv && d.nplp > 1;
+  if (d.miso) return multi ? launch_ofdm_f<N, FMT, true, true>(d, io, s) : launch_ofdm_f<N, FMT, false, true>(d, io, s);
+  return multi ? launch_ofdm_f<N, FMT, true, false>(d, io, s) : launch_ofdm_f<N, FMT, false, false>(d, io, s);
 }
 template <int N>
 static hipError_t launch_ofdm_t(const OfdmDev &d, const OfdmIO &io, hipStream_t s) {

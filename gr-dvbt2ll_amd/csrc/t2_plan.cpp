@@ -1060,7 +1060,11 @@ int build_pilot(const PgParams &p, PilotPlan &pp) {
     return -1;
   if (!c.c_data) return -1;
   bool miso = !(p.preamble == 0 || p.preamble == 3);
-  bool tx2 = miso && p.misogroup == 1;
+  // misogroup: 0 TX1, 1 TX2 (group 2's pilots, payload unchanged), 2 TX2 with MISO processing of the payload
+  // (t2_plan.h MISO_TX2_PROCESSED; a MISO preamble only)
+  if (p.misogroup < 0 || p.misogroup > MISO_TX2_PROCESSED || (p.misogroup == MISO_TX2_PROCESSED && !miso)) return -1;
+  const bool proc = p.misogroup == MISO_TX2_PROCESSED;
+  bool tx2 = miso && (p.misogroup == 1 || proc);
   bool ext = p.carriermode == 1 && N >= 8192;
   pp.N_P2 = c.n_p2;
   // carriers (pilotgen:120-175)
@@ -1194,6 +1198,28 @@ int build_pilot(const PgParams &p, PilotPlan &pp) {
     }
   }
   if (consumed != pp.active) return -1;   // carrier maps must agree with C_P2/C_DATA/N_FC
+  pp.miso_proc = proc ? 1 : 0;
+  if (proc) {
+    // MISO processing (9.1): the carrier of payload position p (carrier order within the symbol) takes the
+    // cell of position p ^ 1, selector 1 at even p (-conj: real sign), 0 at odd p (conj: imaginary sign)
+    for (int j = 0; j < pp.Nsym; j++) {
+      int32_t *row = &pp.bin_map[(size_t)j * N];
+      int first = -1, n = 0;
+      for (int cc = 0; cc < C_PS; cc++) {
+        const int32_t c = row[(pp.left_nulls + cc + N / 2) % N];
+        if (c < 0) continue;
+        if (first < 0) first = c;
+        n++;
+      }
+      if (n & 1) return -1;   // pairs need an even payload count (true of every C_P2, C_DATA, N_FC of the standard)
+      for (int cc = 0; cc < C_PS; cc++) {
+        int32_t &c = row[(pp.left_nulls + cc + N / 2) % N];
+        if (c < 0) continue;
+        const int pos = c - first;
+        c = (first + (pos ^ 1)) | (int32_t)((pos & 1) ^ 1) << MISO_MAP_SEL_BIT;
+      }
+    }
+  }
   switch (p.guardinterval) {
     case GI132: pp.G = N / 32; break;
     case GI116: pp.G = N / 16; break;
@@ -1362,12 +1388,24 @@ int build_chain_layout(const FramePlan &fp, const PilotPlan &pp, ChainLayout &cl
   const FrameClass &fc = fp.cls[cls];
   const int S = fc.S;
   // bins -> frame data order (TI output) via the framemapper's composed map
+  // (MISO-processed frames: a payload bin's code names its partner's cell and a selector, kept beside the
+  // map in csel; everything below then follows the partner's destination bin)
   std::vector<int32_t> nat(pp.bin_map.size());
+  std::vector<int32_t> sel(pp.miso_proc ? nat.size() : 0);
   for (size_t i = 0; i < nat.size(); i++) {
     int32_t c = pp.bin_map[i];
+    if (pp.miso_proc && c >= 0) {
+      sel[i] = 2 | (c >> MISO_MAP_SEL_BIT);
+      c &= MISO_MAP_MASK;
+    }
     nat[i] = c >= 0 ? fc.gather_d[c] : c;
   }
   cl.cmap = ofdm_stored_rows(pp.N, pp.Nsym, nat);
+  cl.csel.clear();
+  if (pp.miso_proc) {
+    const std::vector<int32_t> ssel = ofdm_stored_rows(pp.N, pp.Nsym, sel);
+    cl.csel.assign(ssel.begin(), ssel.end());
+  }
   cl.inv.assign(S, 0);
   cl.sym_d0.assign(pp.Nsym, 0);
   cl.sym_n.assign(pp.Nsym, 0);
@@ -1460,6 +1498,9 @@ int build_chain_layout(const FramePlan &fp, const PilotPlan &pp, ChainLayout &cl
   cl.inv.swap(inv2);
   for (auto &c : cl.cmap)
     if (c >= 0) c = cl.part[c];
+  if (pp.miso_proc)   // the data slots' selectors ride in the bins' free top bit
+    for (size_t i = 0; i < cl.cmap.size(); i++)
+      if (cl.cmap[i] >= 0) cl.inv[cl.cmap[i]] |= (uint16_t)((cl.csel[i] & 1) << MISO_INV_SEL_BIT);
   return 0;
 }
 
@@ -1486,15 +1527,24 @@ int build_aux_lists(const ChainLayout &cl, int N, int Nsym, const std::vector<cf
     al.grp[4 * g + 2] = (int32_t)al.ind.size();
     if (h && !split) continue;
     const int32_t *row = &cl.cmap[(size_t)j * N + (size_t)h * nsub];
+    // MISO-processed frames: the payload bins' selectors (0: not payload); their aux cells (L1, dummy and
+    // thinning cells) are sent with one sign flipped (t2_plan.h miso_flip), zeros included
+    const uint8_t *srow = cl.csel.empty() ? nullptr : &cl.csel[(size_t)j * N + (size_t)h * nsub];
+    auto value = [&](int k, int a) {
+      const cf32 v = auxv[a];
+      return srow && srow[k] ? miso_flip(v, srow[k] & 1) : v;
+    };
     // zero bins: AUX_ZERO, or an aux cell that is +0 in every variant
     auto is_zero = [&](int k) {
       const int32_t c = row[k];
       if (c >= 0) return false;
-      if (c == -AUX_ZERO - 1) return true;
+      const bool payload = srow && srow[k];
+      if (c == -AUX_ZERO - 1 && !payload) return true;
       const int a = -c - 1;
       if (a >= aux_len || !same_in_all(a)) return false;
+      const cf32 v = value(k, a);
       uint64_t bits;
-      std::memcpy(&bits, &auxv[a], sizeof(bits));
+      std::memcpy(&bits, &v, sizeof(bits));
       return bits == 0;
     };
     int z0 = 0, z1 = 0;
@@ -1519,7 +1569,7 @@ int build_aux_lists(const ChainLayout &cl, int N, int Nsym, const std::vector<cf
       const int a = -c - 1;
       if (a >= aux_len) return -1;
       if (same_in_all(a)) {
-        const cf32 v = auxv[a];
+        const cf32 v = value(k, a);
         al.dbin.push_back((uint16_t)k);
         al.dval.push_back(v);
       } else {
@@ -1527,7 +1577,12 @@ int build_aux_lists(const ChainLayout &cl, int N, int Nsym, const std::vector<cf
         // range) aux index a of the frame's t2_frame_num variant (code a + 1)
         const int code = is_l1(a) ? a - l1_lo + 1 : a + 1;
         if (code >= (1 << 17)) return -1;
-        al.ind.push_back((uint32_t)k | ((uint32_t)code << 15));
+        uint32_t e = (uint32_t)k | ((uint32_t)code << 15);
+        if (srow && srow[k]) {   // processed: the selector in the top bit, above a 16-bit code
+          if (code >= (1 << 16)) return -1;
+          e |= (uint32_t)(srow[k] & 1) << MISO_IND_SEL_BIT;
+        }
+        al.ind.push_back(e);
       }
     }
     {   // the group's direct entries in the order the kernel's quad write groups want (bank_balance)

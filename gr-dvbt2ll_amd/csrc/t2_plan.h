@@ -185,9 +185,30 @@ struct PgParams {
   int carriermode, fftsize, pilotpattern, guardinterval, numdatasyms, paprmode, version, preamble,
       misogroup, equalization, bandwidth, vlength;
 };
+// MISO processing of transmitter group 2's payload cells (EN 302 755 9.1; misogroup 2 = MISO_TX2_PROCESSED):
+// with a_p, p < n, a symbol's payload cells in carrier order (everything the frame mapper emits for it: L1,
+// data, dummy and thinning cells; n even), the carrier of position p sends e_p, where e_2i = -conj(a_2i+1) and
+// e_2i+1 = conj(a_2i).  So position p's carrier takes the cell of position p ^ 1 with one sign bit flipped:
+// selector 1 (p even) flips the real part's, (x, y) -> (-x, y); selector 0 (p odd) the imaginary part's,
+// (x, y) -> (x, -y); signed zeros included.  The tables carry the selector beside the (partner's) source:
+//   PilotPlan::bin_map     data codes (>= 0): partner cell index | selector << MISO_MAP_SEL_BIT
+//   ChainLayout::inv       partner's data slot -> bin | selector << MISO_INV_SEL_BIT (bins stay below 2^15,
+//                          padded or not: 16384 + 512 for a 32K half, 16384 + 1024 + 64 up to 16K)
+//   AuxLists::dval         direct payload entries (L1-pre, dummy, thinning cells) hold the flipped value
+//   AuxLists::ind          indirect entries (the per-frame L1-post cells): selector << MISO_IND_SEL_BIT,
+//                          their codes then below 2^16
+constexpr int MISO_TX2_PROCESSED = 2;
+constexpr int MISO_MAP_SEL_BIT = 30;
+constexpr int32_t MISO_MAP_MASK = (1 << MISO_MAP_SEL_BIT) - 1;
+constexpr int MISO_INV_SEL_BIT = 15;
+constexpr int MISO_IND_SEL_BIT = 31;
+// the value a processed carrier of selector sel sends for source cell v
+inline cf32 miso_flip(cf32 v, int sel) { return sel ? cf32{-v.re, v.im} : cf32{v.re, -v.im}; }
+
 struct PilotPlan {
   int N = 0, fft = 0, C_PS = 0, K_EXT = 0, K_OFFSET = 0, G = 0, Nsym = 0, N_P2 = 0, active = 0;
   int left_nulls = 0, eq = 0;
+  int miso_proc = 0;                     // MISO-processed payload: bin_map's data codes carry a selector
   float normalization = 0.f;
   cf32 pilot_values[12] = {};            // aux[1..12]
   std::vector<int32_t> bin_map;          // Nsym x N, indexed by IFFT input position k (fftshifted)
@@ -231,6 +252,10 @@ struct ChainLayout {
   // the group's slot range, plp_bnd[g * (nplp + 1) + p], p = 0..nplp (the last = the range's end); a
   // group's slots are PLP-major, so slot s of the group belongs to the PLP p with bnd[p] <= s < bnd[p + 1]
   std::vector<int32_t> plp_bnd;
+  // MISO-processed frames (PilotPlan::miso_proc), else empty: Nsym x N in cmap's order, 0 for a pilot / null /
+  // reserved bin, 2 | selector for a payload bin (cmap then names the partner's slot or aux cell, and inv
+  // carries the data slots' selectors)
+  std::vector<uint8_t> csel;
 };
 // the layout of the T2 frames of class cls
 int build_chain_layout(const FramePlan &fp, const PilotPlan &pp, ChainLayout &cl, int cls = 0);

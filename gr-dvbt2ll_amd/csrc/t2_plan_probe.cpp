@@ -257,6 +257,57 @@ int t2probe_aux_lists(const int *p20, const int *pg3, int *sizes, uint16_t *dbin
   return 0;
 }
 
+// Everything the OFDM kernels' scatter mode reads for the T2 frames of class cls of a (multi-PLP) frame, as
+// t2_capi.cpp chain_build composes it: the class's layout (cmap, inv with the MISO selector bit, the symbol
+// runs, part, plp_bnd, csel) and its aux lists over one aux row (pilot values set, the L1-post range
+// indirect), plus the class's gather_d (mapped cell -> frame data index | aux) and that aux row.
+// sizes (16 ints): [Nsym, N, S of the class, split, nplp, ncls, direct entries, indirect entries, groups,
+// aux_len, first L1-post aux index, Lp, miso_proc, M, unit, 0].  Call with null outputs for the sizes.
+int t2probe_chain_cls(const int *mp, const int *pg3, int cls, int *sizes, int32_t *cmap, uint16_t *inv, int32_t *d0,
+                      int32_t *dn, int32_t *dn0, int32_t *part, int32_t *bnd, uint8_t *csel, uint16_t *dbin,
+                      float *dval, uint32_t *ind, int32_t *grp, int32_t *zrun, int32_t *gather_d, float *auxrow) {
+  FmParams f;
+  std::vector<PlpParams> plps;
+  int nss = 1;
+  if (!parse_mplp(mp, f, plps, &nss)) return -1;
+  PgParams g{f.carriermode, f.fftsize, f.pilotpattern, f.guardinterval, f.numdatasyms, f.paprmode, f.version,
+             f.preamble, pg3[0], pg3[1], pg3[2], fft_points(f.fftsize)};
+  FramePlan fp;
+  PilotPlan pp;
+  ChainLayout cl;
+  if (build_frame_mplp(f, plps, fp, false, nss) || build_pilot(g, pp)) return -1;
+  if (cls < 0 || cls >= fp.ncls || build_chain_layout(fp, pp, cl, cls)) return -2;
+  std::vector<cf32> row = fp.aux;
+  for (int i = 0; i < 12; i++) row[AUX_PILOT0 + i] = pp.pilot_values[i];
+  AuxLists al;
+  if (build_aux_lists(cl, pp.N, pp.Nsym, row, fp.aux_len, 1, al, AUX_L1PRE + 1840, fp.Lp)) return -3;
+  const int v[16] = {pp.Nsym, pp.N, fp.cls[cls].S, ofdm_split(pp.N) ? 1 : 0, fp.nplp, fp.ncls, (int)al.dbin.size(),
+                     (int)al.ind.size(), (int)al.grp.size() / 4, fp.aux_len, AUX_L1PRE + 1840, fp.Lp, pp.miso_proc,
+                     fp.M, fp.unit, 0};
+  memcpy(sizes, v, sizeof(v));
+  if (cmap) memcpy(cmap, cl.cmap.data(), cl.cmap.size() * 4);
+  if (inv) memcpy(inv, cl.inv.data(), cl.inv.size() * 2);
+  if (d0) memcpy(d0, cl.sym_d0.data(), cl.sym_d0.size() * 4);
+  if (dn) memcpy(dn, cl.sym_n.data(), cl.sym_n.size() * 4);
+  if (dn0) memcpy(dn0, cl.sym_n0.data(), cl.sym_n0.size() * 4);
+  if (part) memcpy(part, cl.part.data(), cl.part.size() * 4);
+  if (bnd) memcpy(bnd, cl.plp_bnd.data(), cl.plp_bnd.size() * 4);
+  if (csel) {
+    if (cl.csel.empty())
+      memset(csel, 0, cl.cmap.size());
+    else
+      memcpy(csel, cl.csel.data(), cl.csel.size());
+  }
+  if (dbin) memcpy(dbin, al.dbin.data(), al.dbin.size() * 2);
+  if (dval) memcpy(dval, al.dval.data(), al.dval.size() * 8);
+  if (ind) memcpy(ind, al.ind.data(), al.ind.size() * 4);
+  if (grp) memcpy(grp, al.grp.data(), al.grp.size() * 4);
+  if (zrun) memcpy(zrun, al.zrun.data(), al.zrun.size() * 4);
+  if (gather_d) memcpy(gather_d, fp.cls[cls].gather_d.data(), fp.cls[cls].gather_d.size() * 4);
+  if (auxrow) memcpy(auxrow, row.data(), (size_t)fp.aux_len * 8);
+  return 0;
+}
+
 // L1-post of one FRAME_IDX: cells from the GPU plan applied on the host in the l1post kernel's
 // order of operations (plan = 1) or from the bit-by-bit host encoder (plan = 0); out: Lp complex.
 // info (optional): [nsig, npost, Lp, mode]

@@ -11,4 +11,5 @@ from .blocks import framemapper_mplp_cc  # noqa: F401
 from .chain import Chain, IQ_CF32, IQ_SC16  # noqa: F401
 from .configs import CONFIGS, T2Config, ts_packets, ts_for_frames  # noqa: F401
 from .configs import MPLP_CONFIGS, MplpConfig, PlpConfig  # noqa: F401
+from .configs import MISO_TX2_PROCESSED  # noqa: F401
 from ._lib import lib, LIB_PATH, EXPORTS, DVBT2Error  # noqa: F401

@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 
 from ._lib import lib, check, _BbParams, _LdpcParams, _ImParams, _FmParams, _PgParams, _MplpParams
+from .configs import MISO_TX2_PROCESSED  # noqa: F401  (a misogroup value pilotgenp1insert_cc accepts)
 
 
 class _Block:
@@ -104,7 +105,8 @@ class framemapperfint_cc(_Block):
 class pilotgenp1insert_cc(_Block):
     """pilotgenp1insert_cc::make(carriermode, fftsize, pilotpattern, guardinterval, numdatasyms,
     paprmode, version, preamble, misogroup, equalization, bandwidth, vlength)
-    (include/dvbt2ll/pilotgenp1insert_cc.h:49): one T2 frame per call -> P1 + OFDM symbols."""
+    (include/dvbt2ll/pilotgenp1insert_cc.h:49): one T2 frame per call -> P1 + OFDM symbols.
+    misogroup MISO_TX2_PROCESSED (MISO preambles): group 2's pilots and the Alamouti-coded payload cells."""
     _name, _params = "pilotgenp1insert", _PgParams
     in_dtype = np.complex64
     out_dtype = np.complex64

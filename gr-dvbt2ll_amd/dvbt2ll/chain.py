@@ -11,6 +11,7 @@ import numpy as np
 
 from ._lib import lib, check, _ChainParams, _ChainInfo, _FmParams, _MplpParams, _MplpChainParams
 from .configs import ts_for_frames, MplpConfig
+from .configs import MISO_TX2_PROCESSED  # noqa: F401  (a cfg.misogroup value the chain accepts)
 
 IQ_CF32 = 0   # DVBT2LL_IQ_CF32
 IQ_SC16 = 1   # DVBT2LL_IQ_SC16

@@ -11,6 +11,11 @@ import numpy as np
 from .enums import *  # noqa: F401,F403
 from . import enums as E
 
+# misogroup beyond gr-dvbt2ll's dvbt2_misogroup_t (so not in enums.py, which mirrors dvbt2ll_config.h):
+# DVBT2LL_MISO_TX2_PROCESSED of include/dvbt2ll_hip.h, transmitter group 2's pilots plus the MISO processing of
+# EN 302 755 9.1 on the payload cells (e_2i = -conj(a_2i+1), e_2i+1 = conj(a_2i)); needs a MISO preamble
+MISO_TX2_PROCESSED = 2
+
 FFT_POINTS = {E.FFTSIZE_1K: 1024, E.FFTSIZE_2K: 2048, E.FFTSIZE_4K: 4096, E.FFTSIZE_8K: 8192,
               E.FFTSIZE_8K_T2GI: 8192, E.FFTSIZE_16K: 16384, E.FFTSIZE_16K_T2GI: 16384,
               E.FFTSIZE_32K: 32768, E.FFTSIZE_32K_T2GI: 32768}

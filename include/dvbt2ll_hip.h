@@ -121,6 +121,20 @@ void dvbt2ll_framemapperfint_destroy(dvbt2ll_framemapperfint *h);
  * guardinterval, numdatasyms, paprmode, version, preamble, misogroup, equalization,
  * bandwidth, vlength) (include/dvbt2ll/pilotgenp1insert_cc.h:49; impl.cc:33-38).
  * ------------------------------------------------------------------------- */
+/* misogroup (here, in dvbt2ll_chain_params and in dvbt2ll_mplp_chain_params) takes gr-dvbt2ll's
+ * dvbt2_misogroup_t values, MISO_TX1 = 0 and MISO_TX2 = 1, which differ in the pilots only (group 2's inverted
+ * scattered / continual / edge pilots and MISO P2 pilots; the payload cells go out unchanged, as in the
+ * reference), and one value beyond the reference:
+ *   DVBT2LL_MISO_TX2_PROCESSED: group 2's pilots plus the MISO processing of EN 302 755 clause 9.1 on the
+ *   payload cells.  With a_p, p < n, the payload cells of an OFDM symbol (every symbol but P1) in carrier
+ *   order -- all the frame mapper emits for it: L1-pre / L1-post, data, dummy and thinning cells, n = C_P2,
+ *   C_DATA or N_FC, always even -- group 2 sends e_2i = -conj(a_2i+1) and e_2i+1 = conj(a_2i) on the carriers
+ *   of a_2i and a_2i+1.  Pilots, reserved tones and unused carriers are untouched; the inverse-sinc
+ *   equalisation applies after it.  Group 1 of the same service is a second handle with MISO_TX1.
+ * DVBT2LL_MISO_TX2_PROCESSED needs a MISO preamble (T2_MISO, T2_LITE_MISO); with a SISO preamble, and for any
+ * misogroup outside 0..2, create returns DVBT2LL_EINVAL.  The reference has no MISO processing block, so the
+ * processed output has no reference parity; it is pinned to the 9.1 rule applied to the reference's cells. */
+#define DVBT2LL_MISO_TX2_PROCESSED 2
 typedef struct dvbt2ll_pilotgenp1insert dvbt2ll_pilotgenp1insert;
 typedef struct {
   int carriermode, fftsize, pilotpattern, guardinterval, numdatasyms, paprmode, version, preamble,
