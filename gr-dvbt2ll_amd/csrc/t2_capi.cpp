@@ -1037,82 +1037,18 @@ static int chain_build(dvbt2ll_chain *h, const FmParams &fm, const std::vector<P
     if ((r = pl->fec.init_chain())) return r;
     if ((r = pl->map.init(q.framesize, q.rate, q.constellation, q.rotation, pl->fec.plan))) return r;
     MapDev &md = pl->map.dev;
-    // the quad table covers one launch unit (fp.unit T2 frames): rows r' = m' F + r for the unit's
-    // interleaving frames m' < fp.unit / cycle and their FEC blocks r
-    const int nif = fp.unit / pp.cycle(), Fu = pp.F * nif;
-    md.F = Fu;
-    if (pp.cs > 0x7FFF) return DVBT2LL_EINVAL;   // 15-bit cell indices in the quad table (<= 32400)
-    // the LDPC + map kernel's cell interleaver + TI store in stored-slot order (layout.part: frame data slot
-    // of each frame data index; a TIME_IL_TYPE 1 PLP's block r writes the P_I T2 frames of its interleaving
-    // frame, frame i's slots at i * pair_stride), in aligned quads of four slots: block r's quads sorted by
-    // slot, each with the cell-interleaver input index of the cell landing in each of its four slots (j with
-    // (ci_perm[j] + ci_shift[r]) mod cs = t, framemapper:1973-1998; 0x8000: a slot of another block, at a
-    // run's edge), its offset from its 64-quad chunk's first quad, each chunk's first quad and the block's
-    // quad count.  A full quad is one 8-byte store, so a store instruction writes 512 B of one or two
-    // contiguous runs (the block's cells in a symbol (half) are one run, bank-balanced inside, t2_plan
-    // build_chain_layout).  A chunk whose quads would span more than 0xFFFF quads (a block's cells in two
-    // T2 frames) ends early: the rest of its 64 entries are empty quads (no store).
-    std::vector<std::vector<std::pair<int64_t, int>>> blk(Fu);
-    std::vector<std::vector<int>> qpos(Fu);   // per block: its quads' entry index (with the chunk padding)
-    int qmax = 0;
-    std::vector<std::pair<int64_t, int>> cells(pp.cs);
-    std::vector<int> jin(pp.cs);   // cell-interleaver input index of each output position t
-    for (int rr = 0; rr < Fu; rr++) {
-      const int r = rr % pp.F, f0 = rr / pp.F * pp.cycle();
-      for (int j = 0; j < pp.cs; j++) jin[(pp.ci_perm[j] + pp.ci_shift[r]) % pp.cs] = j;
-      for (int t = 0; t < pp.cs; t++) {
-        const CellDest cd = cell_dest(fp, k, r, t, f0);
-        const int fu = f0 + cd.off;   // T2 frame of the unit, of class fu mod ncls
-        cells[t] = {(int64_t)fu * h->pair_stride + layouts[fu % fp.ncls].part[cd.pos], jin[t]};
-      }
-      std::sort(cells.begin(), cells.end());
-      auto &qv = blk[rr];   // (quad index, slot-in-quad | t << 2) per cell
-      for (auto &c : cells) qv.push_back({c.first >> 2, (int)(c.first & 3) | (c.second << 2)});
-      int n = -1;
-      int64_t qprev = -1, cbase = 0;
-      for (auto &c : qv) {
-        if (c.first == qprev) continue;
-        qprev = c.first;
-        ++n;
-        if (n % 64 && c.first - cbase > 0xFFFF) n = (n + 63) & ~63;   // start a new chunk here
-        if (n % 64 == 0) cbase = c.first;
-        qpos[rr].push_back(n);
-      }
-      qmax = std::max(qmax, n + 1);
-    }
-    const int qst = (qmax + 63) & ~63, nchk = qst / 64;
-    std::vector<uint32_t> qsrc((size_t)Fu * qst * 2 + 2, 0x80008000u);
-    std::vector<uint16_t> qoff((size_t)Fu * qst + 4, 0);
-    std::vector<int32_t> qb((size_t)Fu * nchk + 1, 0), qn(Fu, 0);
-    for (int rr = 0; rr < Fu; rr++) {
-      int n = -1, qi = -1;
-      int64_t qprev = -1, cbase = 0;
-      for (auto &c : blk[rr]) {
-        if (c.first != qprev) {
-          qprev = c.first;
-          n = qpos[rr][++qi];
-          if (n % 64 == 0) {
-            cbase = c.first;
-            if (cbase > INT32_MAX) return DVBT2LL_EINVAL;
-            qb[(size_t)rr * nchk + n / 64] = (int32_t)cbase;
-          }
-          if (c.first - cbase > 0xFFFF) return DVBT2LL_EINVAL;
-          qoff[(size_t)rr * qst + n] = (uint16_t)(c.first - cbase);
-        }
-        const int sl = c.second & 3, t = c.second >> 2;
-        uint32_t &w = qsrc[((size_t)rr * qst + n) * 2 + (sl >> 1)];
-        w = (w & ~(0xFFFFu << (16 * (sl & 1)))) | ((uint32_t)t << (16 * (sl & 1)));
-      }
-      qn[rr] = n + 1;
-    }
-    if ((r = upload(pl->part, qsrc)) || (r = upload(pl->pbase, qb)) || (r = upload(pl->poff, qoff)) ||
-        (r = upload(pl->pnq, qn)))
+    // the LDPC + map kernel's cell interleaver + TI store as a quad table over one launch unit (t2_plan.h QuadTable)
+    QuadTable qt;
+    if (build_quad_table(fp, layouts, k, h->pair_stride, qt)) return DVBT2LL_EINVAL;
+    md.F = qt.rows;
+    if ((r = upload(pl->part, qt.qsrc)) || (r = upload(pl->pbase, qt.qb)) || (r = upload(pl->poff, qt.qoff)) ||
+        (r = upload(pl->pnq, qt.qn)))
       return r;
     md.slot_quad = pl->part.as<uint2>();
     md.slot_qoff = pl->poff.as<uint16_t>();
     md.slot_qbase = pl->pbase.as<int32_t>();
     md.slot_nq = pl->pnq.as<int32_t>();
-    md.slot_stride = qst;
+    md.slot_stride = qt.stride;
     pl->F = pp.F;
     pl->P = pp.P;
     pl->cyc = pp.cycle();

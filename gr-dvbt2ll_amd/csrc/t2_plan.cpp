@@ -8,6 +8,7 @@
 #include <cstring>
 #include <algorithm>
 #include <numeric>
+#include <utility>
 
 #include "gen/dvbt2_std_tables.h"
 
@@ -1608,6 +1609,77 @@ int build_aux_lists(const ChainLayout &cl, int N, int Nsym, const std::vector<cf
     al.grp[4 * g + 1] = (int32_t)al.dbin.size() - al.grp[4 * g + 0];
     al.grp[4 * g + 3] = (int32_t)al.ind.size() - al.grp[4 * g + 2];
   }
+  return 0;
+}
+
+// the LDPC + map kernel's quad table of PLP plp (the contract: tests/test_cpu_quad_table.py)
+int build_quad_table(const FramePlan &fp, const std::vector<ChainLayout> &layouts, int plp, int64_t pair_stride,
+                     QuadTable &qt) {
+  if (plp < 0 || plp >= fp.nplp || (int)layouts.size() != fp.ncls) return -1;
+  const PlpPlan &pp = fp.plp[plp];
+  if (pp.cs > 0x7FFF) return -1;   // 15-bit cell indices
+  // the table covers one launch unit (fp.unit T2 frames): rows r' = m' F + r for the unit's interleaving
+  // frames m' < fp.unit / cycle and their FEC blocks r
+  const int nif = fp.unit / pp.cycle(), Fu = pp.F * nif;
+  std::vector<std::vector<std::pair<int64_t, int>>> blk(Fu);
+  std::vector<std::vector<int>> qpos(Fu);   // per block: its quads' entry index (with the chunk padding)
+  int qmax = 0;
+  std::vector<std::pair<int64_t, int>> cells(pp.cs);
+  std::vector<int> jin(pp.cs);   // cell-interleaver input index of each output position t
+  for (int rr = 0; rr < Fu; rr++) {
+    const int r = rr % pp.F, f0 = rr / pp.F * pp.cycle();
+    for (int j = 0; j < pp.cs; j++) jin[(pp.ci_perm[j] + pp.ci_shift[r]) % pp.cs] = j;
+    for (int t = 0; t < pp.cs; t++) {
+      const CellDest cd = cell_dest(fp, plp, r, t, f0);
+      const int fu = f0 + cd.off;   // T2 frame of the unit, of class fu mod ncls
+      cells[t] = {(int64_t)fu * pair_stride + layouts[fu % fp.ncls].part[cd.pos], jin[t]};
+    }
+    std::sort(cells.begin(), cells.end());
+    auto &qv = blk[rr];   // (quad index, slot-in-quad | t << 2) per cell
+    for (auto &c : cells) qv.push_back({c.first >> 2, (int)(c.first & 3) | (c.second << 2)});
+    int n = -1;
+    int64_t qprev = -1, cbase = 0;
+    for (auto &c : qv) {
+      if (c.first == qprev) continue;
+      qprev = c.first;
+      ++n;
+      if (n % 64 && c.first - cbase > 0xFFFF) n = (n + 63) & ~63;   // start a new chunk here
+      if (n % 64 == 0) cbase = c.first;
+      qpos[rr].push_back(n);
+    }
+    qmax = std::max(qmax, n + 1);
+  }
+  const int qst = (qmax + 63) & ~63, nchk = qst / 64;
+  std::vector<uint32_t> qsrc((size_t)Fu * qst * 2 + 2, 0x80008000u);
+  std::vector<uint16_t> qoff((size_t)Fu * qst + 4, 0);
+  std::vector<int32_t> qb((size_t)Fu * nchk + 1, 0), qn(Fu, 0);
+  for (int rr = 0; rr < Fu; rr++) {
+    int n = -1, qi = -1;
+    int64_t qprev = -1, cbase = 0;
+    for (auto &c : blk[rr]) {
+      if (c.first != qprev) {
+        qprev = c.first;
+        n = qpos[rr][++qi];
+        if (n % 64 == 0) {
+          cbase = c.first;
+          if (cbase > INT32_MAX) return -1;
+          qb[(size_t)rr * nchk + n / 64] = (int32_t)cbase;
+        }
+        if (c.first - cbase > 0xFFFF) return -1;
+        qoff[(size_t)rr * qst + n] = (uint16_t)(c.first - cbase);
+      }
+      const int sl = c.second & 3, t = c.second >> 2;
+      uint32_t &w = qsrc[((size_t)rr * qst + n) * 2 + (sl >> 1)];
+      w = (w & ~(0xFFFFu << (16 * (sl & 1)))) | ((uint32_t)t << (16 * (sl & 1)));
+    }
+    qn[rr] = n + 1;
+  }
+  qt.rows = Fu;
+  qt.stride = qst;
+  qt.qsrc = std::move(qsrc);
+  qt.qoff = std::move(qoff);
+  qt.qb = std::move(qb);
+  qt.qn = std::move(qn);
   return 0;
 }
 

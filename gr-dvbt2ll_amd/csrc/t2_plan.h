@@ -302,6 +302,27 @@ inline CellDest cell_dest(const FramePlan &fp, int plp, int r, int t, int64_t f0
   return CellDest{off, plp_cell_pos(fp, plp, (int)(u % pl.S), (int)((f0 + off) % fp.ncls))};
 }
 
+// The LDPC + map kernel's cell interleaver + TI store of PLP plp in stored-slot order (ChainLayout::part: frame
+// data slot of each frame data index; a TIME_IL_TYPE 1 PLP's block r writes the P_I T2 frames of its interleaving
+// frame, frame i's slots at i * pair_stride), in aligned quads of four slots.  The table covers one launch unit
+// (fp.unit T2 frames): rows r' = m' F + r for the unit's interleaving frames m' < fp.unit / cycle and their FEC
+// blocks r.  Row r': the block's quads sorted by slot, each with the cell-interleaver input index of the cell
+// landing in each of its four slots (j with (ci_perm[j] + ci_shift[r]) mod cs = t, framemapper:1973-1998; 0x8000:
+// a slot of another block, at a run's edge), its offset from its 64-quad chunk's first quad, each chunk's first
+// quad and the block's quad count.  A full quad is one 8-byte store, so a store instruction writes 512 B of one
+// or two contiguous runs (the block's cells in a symbol (half) are one run, bank-balanced inside,
+// build_chain_layout).  A chunk whose quads would span more than 0xFFFF quads (a block's cells in two T2 frames)
+// ends early: the rest of its 64 entries are empty quads (no store).
+struct QuadTable {
+  int rows = 0, stride = 0;        // F x interleaving frames per unit; entries per row (a multiple of 64)
+  std::vector<uint32_t> qsrc;      // rows x stride x 2 (+ 2): slots 0, 1 | slots 2, 3 of each quad, 16 bits each
+  std::vector<uint16_t> qoff;      // rows x stride (+ 4): quad offset from its chunk's first quad
+  std::vector<int32_t> qb, qn;     // rows x stride / 64 (+ 1): each chunk's first quad; rows: quads with the padding
+};
+// layouts: one per frame class (build_chain_layout); nonzero: a quad index or chunk span out of range
+int build_quad_table(const FramePlan &fp, const std::vector<ChainLayout> &layouts, int plp, int64_t pair_stride,
+                     QuadTable &qt);
+
 // framemapper cell counts {N_P2, C_P2, C_DATA, N_FC, C_FC} (framemapper:290-356, 425-915); -1 if invalid
 int frame_cell_counts(int fftsize, int carriermode, int pp, int papr, int gi, int preamble, int out[5]);
 

@@ -222,6 +222,54 @@ int t2probe_chain(const int *p20, const int *pg3, int *info, int32_t *cmap, uint
   return 0;
 }
 
+// The LDPC + map kernel's quad table of PLP plp as t2_capi.cpp chain_build composes it: the frame of fm's common
+// fields with plps' PLPs, one layout per frame class, pair_stride = the frame's data slots rounded up to 8.
+// sizes (32 x int64): [rows, stride, pair_stride, unit, ncls, cs, F, cycle, qsrc words, qoff entries, qb entries,
+// FIRST_FRAME_IDX, I_JUMP, P_I, 0, 0, S of frame class 0 .. 15].  Call with null outputs for the sizes.
+static int quad_probe(const FmParams &f, const std::vector<PlpParams> &plps, int nss, const int *pg3, int plp,
+                      int64_t *sizes, uint32_t *qsrc, uint16_t *qoff, int32_t *qb, int32_t *qn) {
+  PgParams g{f.carriermode, f.fftsize, f.pilotpattern, f.guardinterval, f.numdatasyms, f.paprmode, f.version,
+             f.preamble, pg3[0], pg3[1], pg3[2], fft_points(f.fftsize)};
+  FramePlan fp;
+  PilotPlan pp;
+  if (build_frame_mplp(f, plps, fp, false, nss) || build_pilot(g, pp)) return -1;
+  if (plp < 0 || plp >= fp.nplp || fp.ncls > 16) return -1;
+  std::vector<ChainLayout> layouts(fp.ncls);
+  for (int c = 0; c < fp.ncls; c++)
+    if (build_chain_layout(fp, pp, layouts[c], c)) return -1;
+  const int64_t pair_stride = ((int64_t)fp.S + 7) / 8 * 8;
+  QuadTable qt;
+  if (build_quad_table(fp, layouts, plp, pair_stride, qt)) return -2;
+  const PlpPlan &pl = fp.plp[plp];
+  const int64_t v[16] = {qt.rows, qt.stride, pair_stride, fp.unit, fp.ncls, pl.cs, pl.F, pl.cycle(),
+                         (int64_t)qt.qsrc.size(), (int64_t)qt.qoff.size(), (int64_t)qt.qb.size(), pl.FF, pl.I, pl.P,
+                         0, 0};
+  memcpy(sizes, v, sizeof(v));
+  for (int c = 0; c < 16; c++) sizes[16 + c] = c < fp.ncls ? fp.cls[c].S : 0;
+  if (qsrc) memcpy(qsrc, qt.qsrc.data(), qt.qsrc.size() * 4);
+  if (qoff) memcpy(qoff, qt.qoff.data(), qt.qoff.size() * 2);
+  if (qb) memcpy(qb, qt.qb.data(), qt.qb.size() * 4);
+  if (qn) memcpy(qn, qt.qn.data(), qt.qn.size() * 4);
+  return 0;
+}
+// single-PLP chain (dvbt2ll_chain_create: the frame mapper's own PLP)
+int t2probe_quad_table(const int *p20, const int *pg3, int64_t *sizes, uint32_t *qsrc, uint16_t *qoff, int32_t *qb,
+                       int32_t *qn) {
+  FmParams f{p20[0], p20[1], p20[2], p20[3], p20[4], p20[5], p20[6], p20[7], p20[8], p20[9],
+             p20[10], p20[11], p20[12], p20[13], p20[14], p20[15], p20[16], p20[17], p20[18], p20[19]};
+  const PlpParams one{f.framesize, f.rate, f.constellation, f.rotation, f.fecblocks, f.tiblocks, f.inputmode, f.inband};
+  return quad_probe(f, {one}, 1, pg3, 0, sizes, qsrc, qoff, qb, qn);
+}
+// multi-PLP chain (dvbt2ll_chain_create_mplp), PLP plp
+int t2probe_quad_table_mplp(const int *mp, const int *pg3, int plp, int64_t *sizes, uint32_t *qsrc, uint16_t *qoff,
+                            int32_t *qb, int32_t *qn) {
+  FmParams f;
+  std::vector<PlpParams> plps;
+  int nss = 1;
+  if (!parse_mplp(mp, f, plps, &nss)) return -1;
+  return quad_probe(f, plps, nss, pg3, plp, sizes, qsrc, qoff, qb, qn);
+}
+
 // the fused chain's compact aux lists (build_aux_lists) over the per-variant aux table the chain
 // uploads (frame aux cells with the 12 pilot values in every variant, as t2_capi.cpp composes
 // it).  Call with null outputs first: sizes = [dbin entries, ind entries, groups, aux_len,

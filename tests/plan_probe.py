@@ -37,6 +37,8 @@ def lib():
         L.t2probe_chain_mplp.argtypes = [vp] * 10
         L.t2probe_l1post_mplp.argtypes = [vp, ctypes.c_int, vp, vp]
         L.t2probe_l1post_bits_mplp.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int]
+        L.t2probe_quad_table.argtypes = [vp] * 7
+        L.t2probe_quad_table_mplp.argtypes = [vp, vp, ctypes.c_int] + [vp] * 5
         _L = L
     return _L
 
@@ -277,3 +279,35 @@ def l1post_mplp(mcfg, frame_idx):
     out = np.zeros(int(info[2]), np.complex64)
     assert lib().t2probe_l1post_mplp(_p(a), frame_idx, _p(out), _p(info)) == 0
     return out, dict(nsig=int(info[0]), npost=int(info[1]), Lp=int(info[2]))
+
+
+def quad_table(cfg, plp=0):
+    """the LDPC + map kernel's quad table of PLP plp as the chain builds it (t2_plan.h QuadTable; cfg a T2Config or
+    an MplpConfig): quad [rows, stride] uint32 pairs (slots 0, 1 | slots 2, 3, 16 bits each: bits 0..14 the
+    cell-interleaver input index j, bit 15 another block's slot), qoff [rows, stride], qbase [rows, stride / 64],
+    nq [rows], the arrays as uploaded (with their tail padding) in raw, and the geometry: pair_stride, unit,
+    ncls, cs, F, cycle, first_frame_idx, frame_interval, ti_frames, cls_S (data slots of each frame class)"""
+    g = np.array([cfg.misogroup, cfg.equalization, cfg.bandwidth], np.int32)
+    sz = np.zeros(32, np.int64)
+    if hasattr(cfg, "mplp_array"):
+        a = np.array(cfg.mplp_array(), np.int32)
+        call = lambda *o: lib().t2probe_quad_table_mplp(_p(a), _p(g), int(plp), _p(sz), *o)   # noqa: E731
+    else:
+        assert plp == 0
+        a = np.array(cfg.fm_args(), np.int32)
+        call = lambda *o: lib().t2probe_quad_table(_p(a), _p(g), _p(sz), *o)   # noqa: E731
+    if call(None, None, None, None):
+        return None
+    rows, stride = int(sz[0]), int(sz[1])
+    qsrc = np.zeros(int(sz[8]), np.uint32)
+    qoff = np.zeros(int(sz[9]), np.uint16)
+    qb = np.zeros(int(sz[10]), np.int32)
+    qn = np.zeros(rows, np.int32)
+    assert call(_p(qsrc), _p(qoff), _p(qb), _p(qn)) == 0
+    ncls = int(sz[4])
+    return dict(rows=rows, stride=stride, pair_stride=int(sz[2]), unit=int(sz[3]), ncls=ncls, cs=int(sz[5]),
+                F=int(sz[6]), cycle=int(sz[7]), first_frame_idx=int(sz[11]), frame_interval=int(sz[12]),
+                ti_frames=int(sz[13]), cls_S=[int(x) for x in sz[16:16 + ncls]],
+                quad=qsrc[:rows * stride * 2].reshape(rows, stride, 2), qoff=qoff[:rows * stride].reshape(rows, stride),
+                qbase=qb[:rows * (stride // 64)].reshape(rows, stride // 64), nq=qn,
+                raw=dict(quad=qsrc, qoff=qoff, qbase=qb))

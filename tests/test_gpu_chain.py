@@ -337,6 +337,7 @@ def test_chain_streams_rejects_bad_args(gpu):
 
 from dvbt2ll import enums as E  # noqa: E402
 from test_gpu_blocks import ALL_CODES, MODES  # noqa: E402
+from lm_cases import packed_codewords  # noqa: E402
 
 
 CW_CASES = [(m, i, E.MOD_16QAM) for m, i in MODES] + [(E.INPUTMODE_NORMAL, E.INBAND_OFF, E.MOD_QPSK)]
@@ -348,7 +349,6 @@ def test_chain_codewords_all_codes(gpu, framesize, rate, mode, inband, const):
     """the chain's FEC kernels (bbch_kernel: BBFRAMEs + BCH on the matrix cores; ldpc_map_kernel's LDPC
     stage) for every code x input mode: the packed interleaver-input codewords of two frames equal the oracle's bbheaderbch + ldpc
     output (info bits, then the parity interleaved [row a][column c] where the constellation has it)"""
-    import plan_probe as PP
     cfg = CONFIGS["cfg4"].with_(framesize=framesize, rate=rate, inputmode=mode, inband=inband, constellation=const,
                                 fecblocks=3)
     nb = 2 * cfg.fecblocks
@@ -359,14 +359,8 @@ def test_chain_codewords_all_codes(gpu, framesize, rate, mode, inband, const):
     ts, base = ts_for_frames(cfg, 0, 2)
     assert base == 0
     bits, _ = O.BB(*cfg.bb_args()).work(ts, nb)
-    fp = PP.fec_plan(framesize, rate, cfg.constellation)
-    nbch, q = fp["nbch"], fp["q"]
     nldpc = 64800 if framesize else 16200
     cw = O.LDPC(framesize, rate).work(bits, nb).reshape(nb, nldpc)
-    if fp["parity_il"]:
-        t, s = np.divmod(np.arange(nldpc - nbch), 360)
-        cw = cw.copy()
-        cw[:, nbch:] = cw[:, nbch + q * s + t]
-    want = np.packbits(cw, axis=1)
+    want = packed_codewords(framesize, rate, cfg.constellation, cw)
     bad = np.nonzero((got[:, :nldpc // 8] != want).any(axis=1))[0]
     assert bad.size == 0, ("blocks", bad.tolist())
