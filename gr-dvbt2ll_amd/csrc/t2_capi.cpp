@@ -781,6 +781,14 @@ struct dvbt2ll_chain {
   DevBuf abin, aval, aind, agrp, azr;   // non-data bins as compact lists (t2_plan.h AuxLists)
   DevBuf plp_bnd, plp_qbase, qam_all;   // multi-PLP frames: slot ranges per PLP, the PLPs' constellations
   DevBuf cls_inv;                       // per frame class: its data slots' bins at inv + cls_inv[c]
+  // MISO pair chain (dvbt2ll_chain_create_miso_pair): both transmitter groups from one FEC + map pass.  pilot /
+  // ofdm are group 1's (MISO_TX1); group 2's (MISO_TX2_PROCESSED) OFDM launch reads the same index pairs and L1-post
+  // cells through tables of its own over group 1's slot order (t2_plan.h build_pair_layout): its bins, aux lists
+  // and, at 32K, the cross lists.  The symbol runs, PLP boundaries, class offsets and constellations are shared.
+  bool pair = false;
+  PilotPlan pilot2;
+  OfdmTables ofdm2;
+  DevBuf inv2, abin2, aval2, aind2, agrp2, azr2, xent, xgrp;
   std::vector<int32_t> plp_bnd_host;
   std::vector<int> qbase_host;
   DevBuf sync_err;                      // TS sync bytes != 0x47 consumed by run calls (bbheader:675, 703)
@@ -852,9 +860,10 @@ struct dvbt2ll_chain {
   }
   // the chain's kernels on stream s: every PLP's BB + matrix-core BCH kernel, every PLP's LDPC + map
   // (PLP 0's launch has the extra workgroups that generate the frames' L1-post cells), OFDM.  ev1, ev2
-  // (timing): recorded after the BB + BCH kernels and after the LDPC + map kernels
+  // (timing): recorded after the BB + BCH kernels and after the LDPC + map kernels.  A pair handle: oio2 is group
+  // 2's OFDM launch over the same pairs and L1-post cells; a group whose output pointer is null is skipped
   hipError_t launch_chain(const L1IO &lio, const FecIO *fio, const MapIO *mio, const OfdmIO &oio, hipStream_t s,
-                          hipEvent_t ev1, hipEvent_t ev2) {
+                          hipEvent_t ev1, hipEvent_t ev2, const OfdmIO *oio2 = nullptr) {
     hipError_t e = hipSuccess;
     for (int k = 0; k < nplp && e == hipSuccess; k++) e = launch_fec(FEC_TS_TO_BBFRAME, plps[k]->fec.dev, fio[k], s);
     if (e == hipSuccess && ev1) e = hipEventRecord(ev1, s);
@@ -862,7 +871,8 @@ struct dvbt2ll_chain {
       e = k == 0 ? launch_ldpc_map(plps[k]->fec.dev, fio[k], plps[k]->map.dev, mio[k], s, &l1.dev, &lio)
                  : launch_ldpc_map(plps[k]->fec.dev, fio[k], plps[k]->map.dev, mio[k], s);
     if (e == hipSuccess && ev2) e = hipEventRecord(ev2, s);
-    if (e == hipSuccess) e = launch_ofdm(ofdm.dev, oio, s);
+    if (e == hipSuccess && (!pair || oio.out)) e = launch_ofdm(ofdm.dev, oio, s);
+    if (e == hipSuccess && pair && oio2 && oio2->out) e = launch_ofdm(ofdm2.dev, *oio2, s);
     return e;
   }
   // kernel nodes per run: the fused BB + BCH pass and the LDPC + map kernel per PLP, one OFDM
@@ -1003,6 +1013,133 @@ struct dvbt2ll_chain {
   }
 };
 
+// One transmitter group's scatter tables as the OFDM kernels read them, from its layouts (one per frame class) over
+// the aux row auxv: the data slots' bins as padded LDS slots within their half (the kernel writes them as they
+// are), the classes' tables back to back, each class's bins from an 8-slot boundary (the kernel reads aligned quads
+// / octets; cls_inv: each class's offset); the classes' aux lists back to back (a class's dummy cells differ) with
+// the group offsets rebased, their bins and zero runs as padded slots, and the tail padding the kernels' last loads
+// want.  cross (a pair handle's group 2, else null): the classes' cross-listed slots get one of the kernel's dummy
+// LDS slots, the ones after the half's padded bins (t2_kernels.hip), as their bin.
+struct GroupTables {
+  std::vector<uint16_t> inv_pad;
+  std::vector<int32_t> cls_inv, zr;
+  AuxLists al;
+};
+static int group_tables(const FramePlan &fp, const PilotPlan &pp, const std::vector<ChainLayout> &layouts,
+                        const std::vector<CrossLists> *cross, const std::vector<cf32> &auxv, GroupTables &t) {
+  const int nsub_h = ofdm_split(pp.N) ? pp.N / 2 : pp.N;
+  const uint32_t dummy0 = ofdm_padded_bin(pp.N, (uint32_t)nsub_h);
+  // (MISO-processed frames: the selector stays in the padded bin's top bit)
+  const uint16_t selbit = pp.miso_proc ? (uint16_t)(1u << MISO_INV_SEL_BIT) : (uint16_t)0;
+  AuxLists &al = t.al;
+  for (size_t c = 0; c < layouts.size(); c++) {
+    const ChainLayout &lc = layouts[c];
+    t.cls_inv.push_back((int32_t)t.inv_pad.size());
+    for (size_t si = 0; si < lc.inv.size(); si++)
+      t.inv_pad.push_back(cross && (*cross)[c].skip[si]
+                              ? (uint16_t)(dummy0 + (si & 63))
+                              : (uint16_t)(ofdm_padded_bin(pp.N, (lc.inv[si] & ~selbit) % nsub_h) | (lc.inv[si] & selbit)));
+    t.inv_pad.resize(((t.inv_pad.size() + 7) & ~(size_t)7) + 8, 0);
+    AuxLists ac;
+    if (build_aux_lists(lc, pp.N, pp.Nsym, auxv, fp.aux_len, 1, ac, AUX_L1PRE + 1840, fp.Lp)) return DVBT2LL_EINVAL;
+    if (ac.dbin.size() % 4) return DVBT2LL_EINVAL;   // groups of direct quads stay aligned
+    for (size_t g = 0; g + 3 < ac.grp.size(); g += 4) {
+      ac.grp[g] += (int32_t)al.dbin.size();
+      ac.grp[g + 2] += (int32_t)al.ind.size();
+    }
+    al.dbin.insert(al.dbin.end(), ac.dbin.begin(), ac.dbin.end());
+    al.dval.insert(al.dval.end(), ac.dval.begin(), ac.dval.end());
+    al.ind.insert(al.ind.end(), ac.ind.begin(), ac.ind.end());
+    al.grp.insert(al.grp.end(), ac.grp.begin(), ac.grp.end());
+    al.zrun.insert(al.zrun.end(), ac.zrun.begin(), ac.zrun.end());
+  }
+  for (auto &b : al.dbin)
+    if (b != 0xFFFF) b = (uint16_t)ofdm_padded_bin(pp.N, b);
+  for (auto &e : al.ind) e = ofdm_padded_bin(pp.N, e & 0x7FFFu) | (e & ~0x7FFFu);   // (code and selector bits kept)
+  t.zr.assign(al.zrun.size(), 0);   // zero runs as padded slot ranges
+  for (size_t g = 0; g + 1 < al.zrun.size(); g += 2) {
+    const int z0 = al.zrun[g], z1 = al.zrun[g + 1];
+    t.zr[g] = z1 > z0 ? (int32_t)ofdm_padded_bin(pp.N, (uint32_t)z0) : 0;
+    t.zr[g + 1] = z1 > z0 ? (int32_t)ofdm_padded_bin(pp.N, (uint32_t)(z1 - 1)) + 1 : 0;
+  }
+  al.ind.push_back(0);   // never empty (device pointer)
+  al.dbin.resize(al.dbin.size() + 4, 0xFFFF);
+  al.dval.resize(al.dval.size() + 4, cf32{0.f, 0.f});
+  return 0;
+}
+
+// A pair handle's group 2 (MISO_TX2_PROCESSED) after group 1's tables are built: its pilot plan, and per frame
+// class its layout over group 1's slot order (layouts: group 1's; cls_inv: their offsets in the bin table), as
+// device tables.  pg1: group 1's pilot parameters; auxrow: the frame's aux row.
+static_assert(MISO_CROSS_MAX == OFDM_CROSS_MAX, "the planner's cross-list capacity is the 32K kernel's");
+static int chain_build_group2(dvbt2ll_chain *h, const PgParams &pg1, const std::vector<ChainLayout> &layouts,
+                              const std::vector<int32_t> &cls_inv, const std::vector<cf32> &auxrow) {
+  const FramePlan &fp = h->frame;
+  PgParams pg = pg1;
+  pg.misogroup = MISO_TX2_PROCESSED;
+  if (build_pilot(pg, h->pilot2) || h->pilot2.active != fp.M) return DVBT2LL_EINVAL;
+  const PilotPlan &pp = h->pilot2;
+  const bool split = ofdm_split(pp.N);
+  const int nsub_h = split ? pp.N / 2 : pp.N;
+  std::vector<cf32> auxv = auxrow;
+  for (int i = 0; i < 12; i++) auxv[AUX_PILOT0 + i] = pp.pilot_values[i];
+  std::vector<ChainLayout> lay2(fp.ncls);
+  std::vector<CrossLists> cross(fp.ncls);
+  std::vector<uint32_t> xent;
+  std::vector<int32_t> xgrp;
+  for (int c = 0; c < fp.ncls; c++) {
+    const CrossLists &xl = cross[c];
+    if (build_pair_layout(fp, h->pilot, layouts[c], pp, lay2[c], cross[c], c) || xl.max_len > OFDM_CROSS_MAX)
+      return DVBT2LL_EINVAL;
+    for (size_t g = 0; g + 1 < xl.grp.size(); g += 2) {
+      xgrp.push_back(xl.grp[g] + (int32_t)(xent.size() / 2));
+      xgrp.push_back(xl.grp[g + 1]);
+    }
+    for (const CrossEntry &e : xl.ent) {
+      const int qb = h->qbase_host[e.plp];
+      if (e.bin >= nsub_h || qb < 0 || qb > 0xFFFF || e.slot < 0 || e.slot >= h->pair_stride) return DVBT2LL_EINVAL;
+      xent.push_back((uint32_t)e.slot);
+      xent.push_back(ofdm_padded_bin(pp.N, e.bin) | (uint32_t)(e.sel & 1) << 15 | (uint32_t)qb << 16);
+    }
+  }
+  xent.resize(xent.size() + 2, 0);   // never empty (device pointer)
+  GroupTables t;
+  int r;
+  if ((r = group_tables(fp, pp, lay2, &cross, auxv, t))) return r;
+  if (t.cls_inv != cls_inv) return DVBT2LL_EINVAL;   // the classes' offsets are group 1's
+  const std::vector<int32_t> &cmap0 = lay2[0].cmap;
+  const AuxLists &al = t.al;
+  if ((r = h->ofdm2.init(pp, cmap0, fp.aux_len, 1))) return r;
+  if ((r = upload(h->inv2, t.inv_pad)) || (r = upload(h->abin2, al.dbin)) || (r = upload(h->aval2, al.dval)) ||
+      (r = upload(h->aind2, al.ind)) || (r = upload(h->agrp2, al.grp)) || (r = upload(h->azr2, t.zr)) ||
+      (r = upload(h->xent, xent)) || (r = upload(h->xgrp, xgrp)))
+    return r;
+  // the symbol runs, PLP boundaries, class offsets and constellations are group 1's
+  const OfdmDev &o1 = h->ofdm.dev;
+  OfdmDev &od = h->ofdm2.dev;
+  od.inv = h->inv2.as<uint16_t>();
+  od.abin = h->abin2.as<uint16_t>();
+  od.aval = h->aval2.as<float2>();
+  od.aind = h->aind2.as<uint32_t>();
+  od.agrp = h->agrp2.as<int4>();
+  od.azr = h->azr2.as<int2>();
+  od.sym_d0 = o1.sym_d0;
+  od.sym_n = o1.sym_n;
+  od.sym_n0 = o1.sym_n0;
+  od.ncls = o1.ncls;
+  od.cls_inv = o1.cls_inv;
+  od.nplp = o1.nplp;
+  od.qam = o1.qam;
+  od.nq = o1.nq;
+  od.plp_bnd = o1.plp_bnd;
+  od.plp_qbase = o1.plp_qbase;
+  if (split) {   // 32K: the cross lists select the pair kernel
+    od.xent = h->xent.as<uint2>();
+    od.xgrp = h->xgrp.as<int2>();
+  }
+  return 0;
+}
+
 // the common construction of single- and multi-PLP chains: fm's common fields with plps' PLPs
 static int chain_build(dvbt2ll_chain *h, const FmParams &fm, const std::vector<PlpParams> &plps,
                        const std::vector<int> &tsrate, int misogroup, int equalization, int bandwidth, int device,
@@ -1072,63 +1209,30 @@ static int chain_build(dvbt2ll_chain *h, const FmParams &fm, const std::vector<P
     h->qbase_host.push_back(qb0);
     h->plps.push_back(std::move(pl));
   }
-  // stored bins -> padded LDS slots within their half (the kernel writes them as they are), the frame classes'
-  // tables back to back (each class's bins from an 8-slot boundary: the kernel reads aligned quads / octets)
-  const int nsub_h = ofdm_split(h->pilot.N) ? h->pilot.N / 2 : h->pilot.N;
-  std::vector<uint16_t> inv_pad;
-  std::vector<int32_t> cls_inv, sd0, sdn, sdn0, bnd_all;
+  const PilotPlan &pp = h->pilot;
+  // one aux row (pilot values, L1-pre, dummy cells): the L1-post cells come per frame from the GPU
+  std::vector<cf32> auxv = fp.aux;
+  for (int i = 0; i < 12; i++) auxv[AUX_PILOT0 + i] = pp.pilot_values[i];
+  // the data slots' padded bins and the aux lists of every frame class (group_tables), and the classes' symbol runs
+  GroupTables t;
+  if ((r = group_tables(fp, pp, layouts, nullptr, auxv, t))) return r;
+  const std::vector<int32_t> &cls_inv = t.cls_inv;
+  const AuxLists &al = t.al;
+  std::vector<int32_t> sd0, sdn, sdn0, bnd_all;
   for (const ChainLayout &lc : layouts) {
-    cls_inv.push_back((int32_t)inv_pad.size());
-    // (MISO-processed frames: the selector stays in the padded bin's top bit)
-    const uint16_t selbit = h->pilot.miso_proc ? (uint16_t)(1u << MISO_INV_SEL_BIT) : (uint16_t)0;
-    for (size_t si = 0; si < lc.inv.size(); si++)
-      inv_pad.push_back((uint16_t)(ofdm_padded_bin(h->pilot.N, (lc.inv[si] & ~selbit) % nsub_h) | (lc.inv[si] & selbit)));
-    inv_pad.resize(((inv_pad.size() + 7) & ~(size_t)7) + 8, 0);
     sd0.insert(sd0.end(), lc.sym_d0.begin(), lc.sym_d0.end());
     sdn.insert(sdn.end(), lc.sym_n.begin(), lc.sym_n.end());
     sdn0.insert(sdn0.end(), lc.sym_n0.begin(), lc.sym_n0.end());
     bnd_all.insert(bnd_all.end(), lc.plp_bnd.begin(), lc.plp_bnd.end());
   }
-  if ((r = upload(h->inv, inv_pad)) || (r = upload(h->sym_d0, sd0)) || (r = upload(h->sym_n, sdn)) ||
+  if ((r = upload(h->inv, t.inv_pad)) || (r = upload(h->sym_d0, sd0)) || (r = upload(h->sym_n, sdn)) ||
       (r = upload(h->sym_n0, sdn0)) || (r = upload(h->cls_inv, cls_inv)))
     return r;
-  const PilotPlan &pp = h->pilot;
-  // one aux row (pilot values, L1-pre, dummy cells): the L1-post cells come per frame from the GPU
-  std::vector<cf32> auxv = fp.aux;
-  for (int i = 0; i < 12; i++) auxv[AUX_PILOT0 + i] = pp.pilot_values[i];
   if ((r = h->ofdm.init(pp, layout.cmap, fp.aux_len, 1))) return r;
-  // the classes' aux lists back to back (a class's dummy cells differ), group offsets rebased
-  AuxLists al;
-  for (const ChainLayout &lc : layouts) {
-    AuxLists ac;
-    if (build_aux_lists(lc, pp.N, pp.Nsym, auxv, fp.aux_len, 1, ac, AUX_L1PRE + 1840, fp.Lp)) return DVBT2LL_EINVAL;
-    if (ac.dbin.size() % 4) return DVBT2LL_EINVAL;   // groups of direct quads stay aligned
-    for (size_t g = 0; g + 3 < ac.grp.size(); g += 4) {
-      ac.grp[g] += (int32_t)al.dbin.size();
-      ac.grp[g + 2] += (int32_t)al.ind.size();
-    }
-    al.dbin.insert(al.dbin.end(), ac.dbin.begin(), ac.dbin.end());
-    al.dval.insert(al.dval.end(), ac.dval.begin(), ac.dval.end());
-    al.ind.insert(al.ind.end(), ac.ind.begin(), ac.ind.end());
-    al.grp.insert(al.grp.end(), ac.grp.begin(), ac.grp.end());
-    al.zrun.insert(al.zrun.end(), ac.zrun.begin(), ac.zrun.end());
-  }
   if ((r = h->l1.init(fp))) return r;
   h->l1_stride = (uint32_t)((fp.Lp + 3) & ~3);
-  for (auto &b : al.dbin)
-    if (b != 0xFFFF) b = (uint16_t)ofdm_padded_bin(pp.N, b);
-  for (auto &e : al.ind) e = ofdm_padded_bin(pp.N, e & 0x7FFFu) | (e & ~0x7FFFu);   // (code and selector bits kept)
-  std::vector<int32_t> zr(al.zrun.size());   // zero runs as padded slot ranges
-  for (size_t g = 0; g + 1 < al.zrun.size(); g += 2) {
-    const int z0 = al.zrun[g], z1 = al.zrun[g + 1];
-    zr[g] = z1 > z0 ? (int32_t)ofdm_padded_bin(pp.N, (uint32_t)z0) : 0;
-    zr[g + 1] = z1 > z0 ? (int32_t)ofdm_padded_bin(pp.N, (uint32_t)(z1 - 1)) + 1 : 0;
-  }
-  al.ind.push_back(0);   // never empty (device pointer)
-  al.dbin.resize(al.dbin.size() + 4, 0xFFFF);
-  al.dval.resize(al.dval.size() + 4, cf32{0.f, 0.f});
   if ((r = upload(h->abin, al.dbin)) || (r = upload(h->aval, al.dval)) || (r = upload(h->aind, al.ind)) ||
-      (r = upload(h->agrp, al.grp)) || (r = upload(h->azr, zr)))
+      (r = upload(h->agrp, al.grp)) || (r = upload(h->azr, t.zr)))
     return r;
   OfdmDev &od = h->ofdm.dev;
   od.abin = h->abin.as<uint16_t>();
@@ -1157,6 +1261,7 @@ static int chain_build(dvbt2ll_chain *h, const FmParams &fm, const std::vector<P
     od.plp_bnd = h->plp_bnd.as<int32_t>();
     od.plp_qbase = h->plp_qbase.as<int32_t>();
   }
+  if (h->pair && (r = chain_build_group2(h, pg, layouts, cls_inv, auxv))) return r;
   h->iq_per_frame = (int64_t)pp.Nsym * (pp.N + pp.G) + 2048;
   // the OFDM kernel addresses index pairs and aux cells with 32-bit byte offsets
   if ((uint64_t)h->pair_stride * h->max_frames * 2 >= (1ull << 32) || auxv.size() * 8 >= (1ull << 32) ||
@@ -1169,13 +1274,18 @@ static int chain_build(dvbt2ll_chain *h, const FmParams &fm, const std::vector<P
   return 0;
 }
 
-extern "C" int dvbt2ll_chain_create(const dvbt2ll_chain_params *p, int device, dvbt2ll_chain **out) {
+// pair: a MISO pair handle (both transmitter groups): misogroup MISO_TX1 and a MISO preamble (dvbt2_preamble_t
+// T2_MISO = 1, T2_LITE_MISO = 4; the planner's own test, t2_plan.cpp build_pilot), checked before anything is built
+static bool pair_params_ok(int misogroup, int preamble) { return misogroup == 0 && (preamble == 1 || preamble == 4); }
+static int chain_create(const dvbt2ll_chain_params *p, int device, dvbt2ll_chain **out, bool pair) {
   if (!p || !out || p->max_frames < 1) return DVBT2LL_EINVAL;
   *out = nullptr;
+  if (pair && !pair_params_ok(p->misogroup, p->fm.preamble)) return DVBT2LL_EINVAL;
   const dvbt2ll_framemapperfint_params &f = p->fm;
   std::unique_ptr<dvbt2ll_chain> h(new (std::nothrow) dvbt2ll_chain());
   if (!h) return DVBT2LL_ENOMEM;
   h->p = *p;
+  h->pair = pair;
   h->max_frames = p->max_frames;
   const PlpParams one{f.framesize, f.rate, f.constellation, f.rotation, f.fecblocks, f.tiblocks, f.inputmode, f.inband};
   int r = chain_build(h.get(), to_fm(f), {one}, {p->tsrate}, p->misogroup, p->equalization, p->bandwidth, device);
@@ -1184,9 +1294,17 @@ extern "C" int dvbt2ll_chain_create(const dvbt2ll_chain_params *p, int device, d
   return DVBT2LL_OK;
 }
 
-extern "C" int dvbt2ll_chain_create_mplp(const dvbt2ll_mplp_chain_params *p, int device, dvbt2ll_chain **out) {
+extern "C" int dvbt2ll_chain_create(const dvbt2ll_chain_params *p, int device, dvbt2ll_chain **out) {
+  return chain_create(p, device, out, false);
+}
+extern "C" int dvbt2ll_chain_create_miso_pair(const dvbt2ll_chain_params *p, int device, dvbt2ll_chain **out) {
+  return chain_create(p, device, out, true);
+}
+
+static int chain_create_mplp(const dvbt2ll_mplp_chain_params *p, int device, dvbt2ll_chain **out, bool pair) {
   if (!p || !out || p->max_frames < 1) return DVBT2LL_EINVAL;
   *out = nullptr;
+  if (pair && !pair_params_ok(p->misogroup, p->fm.preamble)) return DVBT2LL_EINVAL;
   FmParams fm;
   std::vector<PlpParams> plps;
   std::vector<int> tsrate;
@@ -1194,6 +1312,7 @@ extern "C" int dvbt2ll_chain_create_mplp(const dvbt2ll_mplp_chain_params *p, int
   if (!mplp_to_plan(p->fm, fm, plps, tsrate, &nss)) return DVBT2LL_EINVAL;
   std::unique_ptr<dvbt2ll_chain> h(new (std::nothrow) dvbt2ll_chain());
   if (!h) return DVBT2LL_ENOMEM;
+  h->pair = pair;
   h->max_frames = p->max_frames;
   const dvbt2ll_plp_params &q0 = p->fm.plp[0];
   h->p.fm = dvbt2ll_framemapperfint_params{q0.framesize, q0.rate, q0.constellation, q0.rotation, q0.fecblocks,
@@ -1211,6 +1330,15 @@ extern "C" int dvbt2ll_chain_create_mplp(const dvbt2ll_mplp_chain_params *p, int
   *out = h.release();
   return DVBT2LL_OK;
 }
+
+extern "C" int dvbt2ll_chain_create_mplp(const dvbt2ll_mplp_chain_params *p, int device, dvbt2ll_chain **out) {
+  return chain_create_mplp(p, device, out, false);
+}
+extern "C" int dvbt2ll_chain_create_mplp_miso_pair(const dvbt2ll_mplp_chain_params *p, int device,
+                                                   dvbt2ll_chain **out) {
+  return chain_create_mplp(p, device, out, true);
+}
+extern "C" int dvbt2ll_chain_num_groups(const dvbt2ll_chain *h) { return h ? (h->pair ? 2 : 1) : 0; }
 
 extern "C" int dvbt2ll_chain_unit_frames(const dvbt2ll_chain *h) { return h ? h->frame.unit : 0; }
 
@@ -1260,13 +1388,18 @@ static void ts_span(const ChainPlp &pl, int64_t first, int64_t n, int64_t *lo, i
 
 // one run over nstreams independent single-PLP streams (nplp == 1) or over one frame sequence of
 // every PLP (nstreams == 1): ts[k], base[k], len[k] per PLP (stream s of a batch at ts[0] + s * ts_stride)
+// A pair handle (groups: the *_groups calls) writes group 1's IQ to iq_dev and group 2's to iq2_dev, either of which
+// may be null; an ordinary handle takes iq_dev alone.
 static int chain_run(dvbt2ll_chain *h, const void *const *ts, const int64_t *base, const int64_t *len,
-                     int64_t ts_stride, int nstreams, int64_t first_frame, int nframes, void *iq_dev, void *stream) {
-  if (!h || !ts || !iq_dev || nframes < 1 || nstreams < 1 || (int64_t)nframes * nstreams > h->max_frames ||
-      first_frame < 0 || (nstreams > 1 && (h->nplp > 1 || ts_stride < len[0])))
+                     int64_t ts_stride, int nstreams, int64_t first_frame, int nframes, void *iq_dev, void *stream,
+                     bool groups = false, void *iq2_dev = nullptr) {
+  if (!h || !ts || h->pair != groups || (!iq_dev && !iq2_dev) || (!groups && !iq_dev) || nframes < 1 || nstreams < 1 ||
+      (int64_t)nframes * nstreams > h->max_frames || first_frame < 0 ||
+      (nstreams > 1 && (h->nplp > 1 || ts_stride < len[0])) || (groups && h->use_graph))
     return DVBT2LL_EINVAL;
   // iq_dev is aligned to one output sample (the IQ stores are whole samples, or pairs where the address allows)
-  if ((uintptr_t)iq_dev % (h->ofdm.dev.fmt == DVBT2LL_IQ_SC16 ? 4u : 8u)) return DVBT2LL_EINVAL;
+  const unsigned iq_align = h->ofdm.dev.fmt == DVBT2LL_IQ_SC16 ? 4u : 8u;
+  if ((uintptr_t)iq_dev % iq_align || (uintptr_t)iq2_dev % iq_align) return DVBT2LL_EINVAL;
   // whole interleaving frames of every PLP (TIME_IL_TYPE 1: P_I T2 frames each)
   if (first_frame % h->frame.unit || nframes % h->frame.unit) return DVBT2LL_EINVAL;
   const int nf = nframes * nstreams;   // frames of the launch, stream-major
@@ -1337,6 +1470,8 @@ static int chain_run(dvbt2ll_chain *h, const void *const *ts, const int64_t *bas
   oio.frames_per_stream = nstreams > 1 ? nframes : 0;
   oio.l1 = h->l1buf[slot].as<float2>();
   oio.l1_stride = h->l1_stride;
+  OfdmIO oio2 = oio;   // a pair handle's group 2: the same pairs and L1-post cells into its own IQ buffer
+  oio2.out = (float2 *)iq2_dev;
   if (h->use_graph) {
     int r = h->graph_launch(lio, fio, mio, oio, nf, slot, s);
     if (r) {
@@ -1344,7 +1479,7 @@ static int chain_run(dvbt2ll_chain *h, const void *const *ts, const int64_t *bas
       return r;
     }
   } else {
-    const hipError_t e = h->launch_chain(lio, fio, mio, oio, s, ev[1], ev[2]);
+    const hipError_t e = h->launch_chain(lio, fio, mio, oio, s, ev[1], ev[2], groups ? &oio2 : nullptr);
     if (e != hipSuccess) {
       h->bpart_dirty[slot] = true;
       HIP_TRY(e);
@@ -1375,8 +1510,24 @@ extern "C" int dvbt2ll_chain_run_plps(dvbt2ll_chain *h, const void *const *ts_de
   return chain_run(h, ts_dev, ts_base, ts_len, 0, 1, first_frame, nframes, iq_dev, stream);
 }
 
+extern "C" int dvbt2ll_chain_run_groups(dvbt2ll_chain *h, const void *ts_dev, int64_t ts_stride, int nstreams,
+                                        int64_t ts_base, int64_t ts_len, int64_t first_frame, int nframes,
+                                        void *const iq_dev[2], void *stream) {
+  if (!h || h->nplp != 1 || !iq_dev) return DVBT2LL_EINVAL;
+  const void *ts[1] = {ts_dev};
+  return chain_run(h, ts, &ts_base, &ts_len, ts_stride, nstreams, first_frame, nframes, iq_dev[0], stream, true,
+                   iq_dev[1]);
+}
+
+extern "C" int dvbt2ll_chain_run_plps_groups(dvbt2ll_chain *h, const void *const *ts_dev, const int64_t *ts_base,
+                                             const int64_t *ts_len, int64_t first_frame, int nframes,
+                                             void *const iq_dev[2], void *stream) {
+  if (!h || !ts_dev || !ts_base || !ts_len || !iq_dev) return DVBT2LL_EINVAL;
+  return chain_run(h, ts_dev, ts_base, ts_len, 0, 1, first_frame, nframes, iq_dev[0], stream, true, iq_dev[1]);
+}
+
 extern "C" int dvbt2ll_chain_set_graph(dvbt2ll_chain *h, int enable) {
-  if (!h) return DVBT2LL_EINVAL;
+  if (!h || (h->pair && enable)) return DVBT2LL_EINVAL;   // graph mode: not for pair handles
   h->use_graph = enable != 0;
   return DVBT2LL_OK;
 }
@@ -1406,7 +1557,7 @@ extern "C" int dvbt2ll_chain_set_slots(dvbt2ll_chain *h, int nslots) {
 
 extern "C" int dvbt2ll_chain_run_host(dvbt2ll_chain *h, const void *ts, int64_t ts_base, int64_t ts_len,
                                       int64_t first_frame, int nframes, void *iq) {
-  if (!h || !ts || !iq || nframes < 1 || nframes > h->max_frames || h->nplp != 1) return DVBT2LL_EINVAL;
+  if (!h || !ts || !iq || nframes < 1 || nframes > h->max_frames || h->nplp != 1 || h->pair) return DVBT2LL_EINVAL;
   HIP_TRY(hipSetDevice(h->ctx.device));
   size_t iq_bytes = (size_t)nframes * h->iq_per_frame * (h->ofdm.dev.fmt == DVBT2LL_IQ_SC16 ? 4 : 8);
   if (h->ts_tmp.ensure((size_t)ts_len + 16) || h->iq_tmp.ensure(iq_bytes)) return DVBT2LL_ENOMEM;
@@ -1420,7 +1571,8 @@ extern "C" int dvbt2ll_chain_run_host(dvbt2ll_chain *h, const void *ts, int64_t 
 
 extern "C" int dvbt2ll_chain_run_plps_host(dvbt2ll_chain *h, const void *const *ts, const int64_t *ts_base,
                                            const int64_t *ts_len, int64_t first_frame, int nframes, void *iq) {
-  if (!h || !ts || !ts_base || !ts_len || !iq || nframes < 1 || nframes > h->max_frames) return DVBT2LL_EINVAL;
+  if (!h || !ts || !ts_base || !ts_len || !iq || nframes < 1 || nframes > h->max_frames || h->pair)
+    return DVBT2LL_EINVAL;
   HIP_TRY(hipSetDevice(h->ctx.device));
   const void *dev[DVBT2LL_MAX_PLP];
   for (int k = 0; k < h->nplp; k++) {
@@ -1442,7 +1594,7 @@ extern "C" int dvbt2ll_chain_host_submit(dvbt2ll_chain *h, const void *ts, int64
                                          int64_t first_frame, int nframes, void *iq, int64_t *ticket) {
   // every argument check precedes the first asynchronous operation, so a refused submission leaves no copy
   // of the caller's buffers in flight (the unit check is repeated by chain_run, after the copy-in is queued)
-  if (!h || !ts || !iq || !ticket || h->nplp != 1 || nframes < 1 || nframes > h->max_frames || first_frame < 0 ||
+  if (!h || !ts || !iq || !ticket || h->nplp != 1 || h->pair || nframes < 1 || nframes > h->max_frames || first_frame < 0 ||
       ts_base < 0 || ts_base % 188 || first_frame % h->frame.unit || nframes % h->frame.unit)
     return DVBT2LL_EINVAL;
   const ChainPlp &pl = *h->plps[0];
@@ -1490,7 +1642,7 @@ extern "C" int dvbt2ll_chain_host_wait(dvbt2ll_chain *h, int64_t ticket) {
 
 extern "C" int dvbt2ll_chain_run_host_pipelined(dvbt2ll_chain *h, const void *ts, int64_t ts_base, int64_t ts_len,
                                                 int64_t first_frame, int nframes, void *iq, int chunk_frames) {
-  if (!h || !ts || !iq || nframes < 1 || chunk_frames < 0 || h->nplp != 1) return DVBT2LL_EINVAL;
+  if (!h || !ts || !iq || nframes < 1 || chunk_frames < 0 || h->nplp != 1 || h->pair) return DVBT2LL_EINVAL;
   const int U = h->frame.unit;
   // chunks of whole launch units; every chunk is checked before the first one is submitted
   int c = chunk_frames ? std::min(chunk_frames, h->max_frames) : h->max_frames;
@@ -1538,6 +1690,8 @@ extern "C" int dvbt2ll_chain_set_output(dvbt2ll_chain *h, float gain, int format
   if (!h || !(gain == gain) || (format != DVBT2LL_IQ_CF32 && format != DVBT2LL_IQ_SC16)) return DVBT2LL_EINVAL;
   h->ofdm.dev.gain = gain;
   h->ofdm.dev.fmt = format;
+  h->ofdm2.dev.gain = gain;   // (a pair handle's group 2)
+  h->ofdm2.dev.fmt = format;
   return DVBT2LL_OK;
 }
 

@@ -161,7 +161,18 @@ struct OfdmDev {
   // 15 and 31; aind's codes are then 16 bits), and the cell read through them is stored with one sign bit
   // flipped: selector 0 (x, -y), selector 1 (-x, y).  The direct aux values are flipped on the host.
   int miso;
+  // MISO pair chain, group 2's 32K launch over group 1's slot order (t2_plan.h CrossLists; null: none, the
+  // ordinary kernels).  The slots whose group-2 bin lies in the other stored half have a dummy LDS slot in inv and
+  // are written by the half they land in from its cross list, after that half's slot stream: group 2 (c Nsym + j)
+  // + h of class c is xgrp[..] = {offset, count <= OFDM_CROSS_MAX} into xent; an entry's x = the data slot within
+  // the frame's pair region, y = padded bin | selector << 15 | the slot's PLP's constellation table base << 16.
+  // Non-null selects the pair instantiation of ofdm32_kernel (miso must be set).
+  const uint2 *xent;
+  const int2 *xgrp;
 };
+// entries per cross list: one per 1024-bin block boundary of the 32K row (t2_plan.h MISO_CROSS_MAX, the same value:
+// t2_capi.cpp); the first wave's lanes below it take one entry each
+constexpr int OFDM_CROSS_MAX = 32;
 struct OfdmIO {
   const float2 *data;       // gather mode: aux variants at aux_off, frame f cells at cell_off + f*cell_stride
                             // scatter mode: aux variants only

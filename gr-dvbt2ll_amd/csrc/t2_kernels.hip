@@ -2722,8 +2722,15 @@ __device__ __forceinline__ void o32_store_pairs(const float2 *v, const IqOut<FMT
 
 // 32K symbols, one workgroup per (symbol, frame): scatter mode (the fused chain), gather mode (the
 // pilotgen block: cells already in carrier order) and the carriers-only test hook
-template <int FMT, bool MULTI, bool MISO>
+// CROSS (the MISO pair chain's group-2 launch, instantiations of their own): the data slots are in group 1's
+// order, so the cells whose group-2 bin lies in the other stored half are not written by their own half's stream
+// (their inv entry is a dummy slot) but by the half they land in, from its cross list (OfdmDev::xent): the first
+// wave's lanes load their entry and its index pair before the half's scatter starts, and look the cell up and
+// write its bin once the half's stream is issued, before the barrier that ends the scatter
+template <int FMT, bool MULTI, bool MISO, bool CROSS = false>
 __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
+  static_assert(!CROSS || MISO, "the cross lists belong to the processed group");
+  static_assert(OFDM_CROSS_MAX <= 64, "one cross entry per lane of the first wave");
   constexpr int N = 32768, NT = O32_NT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float2 *lds = (float2 *)smem;
@@ -2789,6 +2796,26 @@ __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
     // (measured and dropped: both halves' scatter inputs prefetched into registers before the
     // first half is written, in one batch or half 1 behind half 0's arrival: +11 % kernel time)
     float2 ev[16], od[16];                        // stage-A inputs m2 = 2 r, 2 r + 1
+    // the half's cross list (CROSS): lane tid < count of the first wave holds its entry in one register, padded
+    // bin | selector << 15 | the slot's index pair << 16 (a lane with no entry: its dummy slot), and with several
+    // PLPs the slot's constellation table base
+    uint32_t xw = dummy, xlb = 0u;
+    auto cross_load = [&](int h) {
+      if (tid >= 64) return;                      // (wave-uniform)
+      const int2 xg = kc(d.xgrp, 2 * jc + h);     // (xg.y <= OFDM_CROSS_MAX: t2_plan CrossLists)
+      xw = dummy;
+      xlb = 0u;
+      if (tid < xg.y) {
+        const uint2 xe = ld_off(d.xent, (uint32_t)(xg.x + tid) * 8u);
+        const uint32_t pr = ld_off(io.pairs, (cbase + xe.x) * 2u);
+        xw = (xe.y & 0xFFFFu) | pr << 16;
+        if (MULTI) xlb = xe.y >> 16;
+      }
+    };
+    auto cross_write = [&]() {
+      if (tid >= 64) return;
+      lds[xw & 0x7FFFu] = miso_flip(make_float2(qre[xlb + ((xw >> 16) & 0xFFu)], qim[xlb + (xw >> 24)]), (xw >> 15) & 1u);
+    };
     {
       const int2 zr = kc(src.azr, 0);
       for (int i = zr.x + tid; i < zr.y; i += NT) lds[i] = make_float2(0.f, 0.f);
@@ -2798,8 +2825,10 @@ __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
       }
       tw1k[tid] = t1k;
       if (tid < 384) tw2[tid] = t2;
+      if (CROSS) cross_load(0);
       lds_barrier();                            // constellation visible to the scatter
       scatter_group<NT, 4, MULTI, MISO>(lds, src, 0, src.d0, src.dn0, dummy, tid);
+      if (CROSS) cross_write();
       lds_barrier();
 #pragma unroll
       for (uint32_t r = 0; r < 16; r++) ev[r] = lds[o32_bin(kin + 1024u * r)];
@@ -2813,7 +2842,9 @@ __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
         __builtin_amdgcn_sched_barrier(0);
         Dft<16>::run(ev);
       };
+      if (CROSS) cross_load(1);
       scatter_group<NT, 4, MULTI, MISO>(lds, src, 1, src.d0 + src.dn0, src.dn - src.dn0, dummy, tid, dft_even);
+      if (CROSS) cross_write();
       lds_barrier();
 #pragma unroll
       for (uint32_t r = 0; r < 16; r++) od[r] = lds[o32_bin(kin + 1024u * r)];
@@ -2860,8 +2891,15 @@ __global__ __launch_bounds__(O32_NT) void ofdm32_kernel(OfdmDev d, OfdmIO io) {
 template <int N, int FMT, bool MULTI, bool MISO>
 static hipError_t launch_ofdm_f(const OfdmDev &d, const OfdmIO &io, hipStream_t s) {
   if (N == 32768) {
-    const void *fn = (const void *)ofdm32_kernel<FMT, MULTI, MISO>;
     const int lds = o32_lds_bytes(d.inv ? d.nq : 256);
+    if (MISO && d.xent) {   // the pair chain's group 2 (launch_ofdm checked the tables)
+      const void *fn = (const void *)ofdm32_kernel<FMT, MULTI, true, true>;
+      hipError_t e = lds_limit(fn, o32_lds_bytes(OFDM_MAX_QAM));
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((ofdm32_kernel<FMT, MULTI, true, true>), dim3(d.Nsym * io.nframes), dim3(O32_NT), lds, s, d, io);
+      return hipGetLastError();
+    }
+    const void *fn = (const void *)ofdm32_kernel<FMT, MULTI, MISO>;
     hipError_t e = lds_limit(fn, o32_lds_bytes(OFDM_MAX_QAM));   // the largest launch
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((ofdm32_kernel<FMT, MULTI, MISO>), dim3(d.Nsym * io.nframes), dim3(O32_NT), lds, s, d, io);
@@ -2896,6 +2934,9 @@ hipError_t launch_ofdm(const OfdmDev &d, const OfdmIO &io, hipStream_t s) {
   if (io.nframes <= 0) return hipSuccess;
   if (d.inv && (d.nq < 1 || d.nq > OFDM_MAX_QAM || d.nplp < 1 || d.nplp > 8 || (d.nplp > 1 && (!d.plp_bnd || !d.plp_qbase)) ||
                 d.ncls < 1 || !d.cls_inv))
+    return hipErrorInvalidValue;
+  // cross lists: the pair chain's group-2 launch at 32K, scatter mode
+  if ((d.xent || d.xgrp) && (!d.xent || !d.xgrp || !d.miso || !d.inv || d.N != 32768 || io.carriers_only))
     return hipErrorInvalidValue;
   switch (d.N) {
     case 1024: return launch_ofdm_t<1024>(d, io, s);

@@ -1505,6 +1505,100 @@ int build_chain_layout(const FramePlan &fp, const PilotPlan &pp, ChainLayout &cl
   return 0;
 }
 
+// group 2's layout over group 1's slot order (t2_plan.h CrossLists)
+int build_pair_layout(const FramePlan &fp, const PilotPlan &pp1, const ChainLayout &cl1, const PilotPlan &pp2,
+                      ChainLayout &cl2, CrossLists &xl, int cls) {
+  if (cls < 0 || cls >= fp.ncls || !pp2.miso_proc || pp1.miso_proc || pp2.active != fp.M || pp1.active != fp.M ||
+      pp2.N != pp1.N || pp2.Nsym != pp1.Nsym || pp2.N > 32768)
+    return -1;
+  const FrameClass &fc = fp.cls[cls];
+  const int S = fc.S, N = pp2.N, Nsym = pp2.Nsym, P = fp.nplp;
+  if ((int)cl1.part.size() != S || (int)cl1.inv.size() != S || (int)cl1.sym_d0.size() != Nsym ||
+      cl1.plp_bnd.size() != (size_t)2 * Nsym * (P + 1))
+    return -1;
+  // bins -> group 1's slots: the partner's cell and the selector, as in build_chain_layout
+  std::vector<int32_t> nat(pp2.bin_map.size()), sel(nat.size());
+  for (size_t i = 0; i < nat.size(); i++) {
+    int32_t c = pp2.bin_map[i];
+    if (c >= 0) {
+      sel[i] = 2 | (c >> MISO_MAP_SEL_BIT);
+      c = fc.gather_d[c & MISO_MAP_MASK];
+      if (c >= 0) c = cl1.part[c];
+    }
+    nat[i] = c;
+  }
+  cl2.cmap = ofdm_stored_rows(N, Nsym, nat);
+  const std::vector<int32_t> ssel = ofdm_stored_rows(N, Nsym, sel);
+  cl2.csel.assign(ssel.begin(), ssel.end());
+  cl2.sym_d0 = cl1.sym_d0;
+  cl2.sym_n = cl1.sym_n;
+  cl2.sym_n0 = cl1.sym_n0;
+  cl2.part = cl1.part;
+  cl2.plp_bnd = cl1.plp_bnd;
+  cl2.inv.assign(S, 0);
+  xl.ent.clear();
+  xl.grp.assign((size_t)4 * Nsym, 0);
+  xl.skip.assign(S, 0);
+  xl.max_len = 0;
+  const bool split = ofdm_split(N);
+  const int half = N / 2;
+  std::vector<char> seen(S, 0);
+  std::vector<CrossEntry> cross[2];
+  for (int j = 0; j < Nsym; j++) {
+    const int d0 = cl1.sym_d0[j], n = cl1.sym_n[j], n0 = cl1.sym_n0[j];
+    cross[0].clear();
+    cross[1].clear();
+    int cnt = 0;
+    for (int k = 0; k < N; k++) {
+      const int32_t s = cl2.cmap[(size_t)j * N + k];
+      if (s < 0) continue;
+      if (s < d0 || s >= d0 + n || seen[s]) return -1;   // a pair's two cells are data cells of one symbol
+      seen[s] = 1;
+      cnt++;
+      const int sl = cl2.csel[(size_t)j * N + k] & 1;
+      cl2.inv[s] = (uint16_t)(k | sl << MISO_INV_SEL_BIT);
+      if (!split) continue;
+      const int h = s - d0 >= n0, h2 = k >= half;
+      if (h == h2) continue;
+      const int32_t *bnd = &cl1.plp_bnd[(size_t)(2 * j + h) * (P + 1)];
+      int p = 0;
+      while (p + 1 < P && s >= bnd[p + 1]) p++;
+      xl.skip[s] = 1;
+      cross[h2].push_back(CrossEntry{s, (uint16_t)(k - h2 * half), (uint8_t)sl, (uint8_t)p});
+    }
+    if (cnt != n) return -1;
+    for (int h = 0; h < 2; h++) {
+      xl.grp[2 * (2 * j + h)] = (int32_t)xl.ent.size();
+      xl.grp[2 * (2 * j + h) + 1] = (int32_t)cross[h].size();
+      xl.max_len = std::max(xl.max_len, (int)cross[h].size());
+      xl.ent.insert(xl.ent.end(), cross[h].begin(), cross[h].end());
+    }
+  }
+  for (int s = 0; s < S; s++)
+    if (!seen[s]) return -1;
+  // the bound: a straddling pair's carriers are neighbours among the payload carriers, one on each side of a
+  // boundary between two 1024-bin blocks of the row; count the boundaries inside the span of active carriers
+  // (carrier c sits at FFT input k = (c + N/2) mod N, so the fftshift wrap k = N - 1 | 0 is a boundary of the
+  // span's middle, and k = N/2 - 1 | N/2, the band edges, is none)
+  xl.bound = 0;
+  if (split) {
+    int cmin = N, cmax = -1;
+    for (int j = 0; j < Nsym; j++)
+      for (int k = 0; k < N; k++)
+        if (pp2.bin_map[(size_t)j * N + k] != -AUX_ZERO - 1 || pp1.bin_map[(size_t)j * N + k] != -AUX_ZERO - 1) {
+          const int c = (k + half) % N;
+          cmin = std::min(cmin, c);
+          cmax = std::max(cmax, c);
+        }
+    for (int b = 0; b < N / 1024; b++) {
+      const int c1 = ((b * 1024 - 1 + N) % N + half) % N, c2 = (b * 1024 + half) % N;
+      if (c2 == c1 + 1 && c1 >= cmin && c2 <= cmax) xl.bound++;
+    }
+  }
+  if (xl.max_len > xl.bound || xl.bound > MISO_CROSS_MAX) return -1;
+  return 0;
+}
+
 int build_aux_lists(const ChainLayout &cl, int N, int Nsym, const std::vector<cf32> &auxv, int aux_len,
                     int t2frames, AuxLists &al, int l1_lo, int l1_len) {
   const bool split = ofdm_split(N);

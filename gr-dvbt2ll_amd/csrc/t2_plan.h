@@ -282,6 +282,39 @@ struct AuxLists {
 // l1post kernel writes); l1_len = 0: indirect codes are aux index + 1 into the frame's variant
 int build_aux_lists(const ChainLayout &cl, int N, int Nsym, const std::vector<cf32> &auxv, int aux_len,
                     int t2frames, AuxLists &al, int l1_lo = 0, int l1_len = 0);
+// MISO pair chain: both transmitter groups from one pair buffer.  Group 2's (MISO_TX2_PROCESSED) layout over group
+// 1's slot order: part, sym_d0, sym_n, sym_n0 and plp_bnd are group 1's (the LDPC + map kernel stores once,
+// through group 1's quad table); inv[s] is the stored bin group 2 sends slot s's cell on (its partner position's
+// carrier) with the selector in MISO_INV_SEL_BIT; cmap names group-1 slots; csel and the aux lists built from the
+// layout (build_aux_lists) are as in the processed layout.
+// 32K: a symbol's run is partitioned by the stored half of group 1's bin.  A slot in half h's run whose group-2 bin
+// lies in half 1 - h (the pairs whose two carriers straddle a 1024-bin block boundary) is skipped by half h's
+// stream (CrossLists::skip; the device table holds a dummy LDS slot in its place) and listed in the cross list of
+// the (symbol, half) group it lands in, which the OFDM kernel writes after that half's stream.
+struct CrossEntry {
+  int32_t slot;    // data slot within the frame's pair region (group 1's order)
+  uint16_t bin;    // stored bin within the half it lands in (unpadded)
+  uint8_t sel;     // selector of the sign flip (miso_flip)
+  uint8_t plp;     // the slot's PLP (its constellation table)
+};
+// entries one OFDM workgroup writes per (symbol, half): one pair per boundary between two 1024-bin blocks of the
+// 32K row, the fftshift wrap included (the kernel's capacity, t2_kernels.h OFDM_CROSS_MAX, is the same value: its
+// first wave's lanes below it take one entry each)
+constexpr int MISO_CROSS_MAX = 32;
+struct CrossLists {
+  std::vector<CrossEntry> ent;
+  std::vector<int32_t> grp;     // 2 per group g = 2 j + h: offset, count
+  std::vector<uint8_t> skip;    // S: 1 = the slot is cross-listed, not streamed
+  int max_len = 0;              // the longest list
+  // block boundaries with an active carrier on both sides in some symbol (from the pilot plan's rows): no list
+  // can be longer, since a straddling pair's two carriers are neighbours among the payload carriers
+  int bound = 0;
+};
+// cl1: build_chain_layout(fp, TX1 pilot plan, cls); pp2: the processed group-2 pilot plan of the same frame.
+// Nonzero: the plans do not belong together, a pair leaves its symbol, or a cross list exceeds its bound.
+int build_pair_layout(const FramePlan &fp, const PilotPlan &pp1, const ChainLayout &cl1, const PilotPlan &pp2,
+                      ChainLayout &cl2, CrossLists &xl, int cls = 0);
+
 // time-interleaver output index (within the interleaving frame, [0, S_if)) of cell-interleaved cell t of FEC
 // block r of PLP plp (framemapper:1999-2028)
 int64_t ti_index(const FramePlan &fp, int plp, int r, int t);

@@ -356,6 +356,66 @@ int t2probe_chain_cls(const int *mp, const int *pg3, int cls, int *sizes, int32_
   return 0;
 }
 
+// The MISO pair chain's group-2 tables over group 1's slot order for the T2 frames of class cls, as t2_capi.cpp
+// chain_build composes them for a pair handle (build_pair_layout over the TX1 layout and the processed group-2
+// pilot plan; pg3[0] is ignored): the outputs of t2probe_chain_cls for that layout, then skip (S: 1 = the slot is
+// cross-listed), the cross entries (4 ints each: slot, bin within its half, selector, PLP) and their groups (2 per
+// group 2 j + h: offset, count).  sizes (20 ints): t2probe_chain_cls's 15, then [15] cross entries, [16] the
+// longest list, [17] the planner's bound, [18] MISO_CROSS_MAX, [19] 0.  Call with null outputs for the sizes.
+int t2probe_pair_cls(const int *mp, const int *pg3, int cls, int *sizes, int32_t *cmap, uint16_t *inv, int32_t *d0,
+                     int32_t *dn, int32_t *dn0, int32_t *part, int32_t *bnd, uint8_t *csel, uint16_t *dbin,
+                     float *dval, uint32_t *ind, int32_t *grp, int32_t *zrun, int32_t *gather_d, float *auxrow,
+                     uint8_t *skip, int32_t *xent, int32_t *xgrp) {
+  FmParams f;
+  std::vector<PlpParams> plps;
+  int nss = 1;
+  if (!parse_mplp(mp, f, plps, &nss)) return -1;
+  PgParams g1{f.carriermode, f.fftsize, f.pilotpattern, f.guardinterval, f.numdatasyms, f.paprmode, f.version,
+              f.preamble, 0, pg3[1], pg3[2], fft_points(f.fftsize)};
+  PgParams g2 = g1;
+  g2.misogroup = MISO_TX2_PROCESSED;
+  FramePlan fp;
+  PilotPlan pp1, pp2;
+  ChainLayout cl1, cl;
+  CrossLists xl;
+  if (build_frame_mplp(f, plps, fp, false, nss) || build_pilot(g1, pp1) || build_pilot(g2, pp2)) return -1;
+  if (cls < 0 || cls >= fp.ncls || build_chain_layout(fp, pp1, cl1, cls)) return -2;
+  if (build_pair_layout(fp, pp1, cl1, pp2, cl, xl, cls)) return -4;
+  std::vector<cf32> row = fp.aux;
+  for (int i = 0; i < 12; i++) row[AUX_PILOT0 + i] = pp2.pilot_values[i];
+  AuxLists al;
+  if (build_aux_lists(cl, pp2.N, pp2.Nsym, row, fp.aux_len, 1, al, AUX_L1PRE + 1840, fp.Lp)) return -3;
+  const int v[20] = {pp2.Nsym, pp2.N, fp.cls[cls].S, ofdm_split(pp2.N) ? 1 : 0, fp.nplp, fp.ncls, (int)al.dbin.size(),
+                     (int)al.ind.size(), (int)al.grp.size() / 4, fp.aux_len, AUX_L1PRE + 1840, fp.Lp, pp2.miso_proc,
+                     fp.M, fp.unit, (int)xl.ent.size(), xl.max_len, xl.bound, MISO_CROSS_MAX, 0};
+  memcpy(sizes, v, sizeof(v));
+  if (cmap) memcpy(cmap, cl.cmap.data(), cl.cmap.size() * 4);
+  if (inv) memcpy(inv, cl.inv.data(), cl.inv.size() * 2);
+  if (d0) memcpy(d0, cl.sym_d0.data(), cl.sym_d0.size() * 4);
+  if (dn) memcpy(dn, cl.sym_n.data(), cl.sym_n.size() * 4);
+  if (dn0) memcpy(dn0, cl.sym_n0.data(), cl.sym_n0.size() * 4);
+  if (part) memcpy(part, cl.part.data(), cl.part.size() * 4);
+  if (bnd) memcpy(bnd, cl.plp_bnd.data(), cl.plp_bnd.size() * 4);
+  if (csel) memcpy(csel, cl.csel.data(), cl.csel.size());
+  if (dbin) memcpy(dbin, al.dbin.data(), al.dbin.size() * 2);
+  if (dval) memcpy(dval, al.dval.data(), al.dval.size() * 8);
+  if (ind) memcpy(ind, al.ind.data(), al.ind.size() * 4);
+  if (grp) memcpy(grp, al.grp.data(), al.grp.size() * 4);
+  if (zrun) memcpy(zrun, al.zrun.data(), al.zrun.size() * 4);
+  if (gather_d) memcpy(gather_d, fp.cls[cls].gather_d.data(), fp.cls[cls].gather_d.size() * 4);
+  if (auxrow) memcpy(auxrow, row.data(), (size_t)fp.aux_len * 8);
+  if (skip) memcpy(skip, xl.skip.data(), xl.skip.size());
+  if (xent)
+    for (size_t i = 0; i < xl.ent.size(); i++) {
+      xent[4 * i] = xl.ent[i].slot;
+      xent[4 * i + 1] = xl.ent[i].bin;
+      xent[4 * i + 2] = xl.ent[i].sel;
+      xent[4 * i + 3] = xl.ent[i].plp;
+    }
+  if (xgrp) memcpy(xgrp, xl.grp.data(), xl.grp.size() * 4);
+  return 0;
+}
+
 // L1-post of one FRAME_IDX: cells from the GPU plan applied on the host in the l1post kernel's
 // order of operations (plan = 1) or from the bit-by-bit host encoder (plan = 0); out: Lp complex.
 // info (optional): [nsig, npost, Lp, mode]

@@ -106,6 +106,8 @@ EXPORTS += ["dvbt2ll_chain_" + f for f in ("host_submit", "host_wait", "run_host
 EXPORTS += ["dvbt2ll_host_alloc", "dvbt2ll_host_free"]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create_mplp", "num_plps", "unit_frames", "get_plp_info", "run_plps",
                                            "debug_plp_codewords", "debug_keep_codewords")]
+EXPORTS += ["dvbt2ll_chain_" + f for f in ("create_miso_pair", "create_mplp_miso_pair", "num_groups", "run_groups",
+                                           "run_plps_groups")]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create", "get_info", "run_device", "run_streams", "run_host", "set_output", "set_slots", "set_graph", "set_timing",
                                            "get_timing", "debug_codewords", "debug_cell_pairs", "debug_cells",
                                            "synchronize", "sync_errors",
@@ -184,6 +186,12 @@ def lib():
     L.dvbt2ll_chain_run_plps.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64), i64, ci,
                                          vp, vp]
     L.dvbt2ll_chain_debug_plp_codewords.argtypes = [vp, ci, vp, i64]
+    L.dvbt2ll_chain_create_miso_pair.argtypes = [ctypes.POINTER(_ChainParams), ci, ctypes.POINTER(vp)]
+    L.dvbt2ll_chain_create_mplp_miso_pair.argtypes = [ctypes.POINTER(_MplpChainParams), ci, ctypes.POINTER(vp)]
+    L.dvbt2ll_chain_num_groups.argtypes = [vp]
+    L.dvbt2ll_chain_run_groups.argtypes = [vp, vp, i64, ci, i64, i64, i64, ci, ctypes.POINTER(vp), vp]
+    L.dvbt2ll_chain_run_plps_groups.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64), i64,
+                                                ci, ctypes.POINTER(vp), vp]
     L.dvbt2ll_chain_destroy.argtypes = [vp]
     L.dvbt2ll_chain_destroy.restype = None
     _lib = L

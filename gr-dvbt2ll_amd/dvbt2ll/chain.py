@@ -18,23 +18,28 @@ IQ_SC16 = 1   # DVBT2LL_IQ_SC16
 
 
 class Chain:
-    def __init__(self, cfg, max_frames=1, device=0):
+    def __init__(self, cfg, max_frames=1, device=0, miso_pair=False):
         """cfg: a T2Config (the reference's single-PLP frame) or an MplpConfig (several data PLPs, Type 1 / 2,
-        TIME_IL_TYPE 0 / 1; dvbt2ll_chain_create_mplp)"""
+        TIME_IL_TYPE 0 / 1; dvbt2ll_chain_create_mplp).  miso_pair: a MISO pair handle, both transmitter groups of
+        one service from one FEC + map pass (cfg.misogroup MISO_TX1, a MISO preamble; run with run_groups /
+        run_groups_device / run_plps_groups; dvbt2ll_chain_create_miso_pair)"""
         self.cfg = cfg
         h = ctypes.c_void_p()
         self._h = None
+        L = lib()
         if isinstance(cfg, MplpConfig):
             p = _MplpChainParams(_MplpParams.from_config(cfg), int(cfg.misogroup), int(cfg.equalization),
                                  int(cfg.bandwidth), int(max_frames))
-            check(lib().dvbt2ll_chain_create_mplp(ctypes.byref(p), int(device), ctypes.byref(h)), "chain create")
+            create = L.dvbt2ll_chain_create_mplp_miso_pair if miso_pair else L.dvbt2ll_chain_create_mplp
         else:
             fm = _FmParams(*[int(v) for v in cfg.fm_args()])
             p = _ChainParams(fm, int(cfg.misogroup), int(cfg.equalization), int(cfg.bandwidth), int(max_frames),
                              int(cfg.tsrate))
-            check(lib().dvbt2ll_chain_create(ctypes.byref(p), int(device), ctypes.byref(h)), "chain create")
+            create = L.dvbt2ll_chain_create_miso_pair if miso_pair else L.dvbt2ll_chain_create
+        check(create(ctypes.byref(p), int(device), ctypes.byref(h)), "chain create")
         self._h = h
         self.max_frames = max_frames
+        self.ngroups = L.dvbt2ll_chain_num_groups(self._h)   # 2 for a MISO pair handle
         self.nplp = lib().dvbt2ll_chain_num_plps(self._h)
         # runs cover whole interleaving frames: first_frame and nframes multiples of unit_frames
         self.unit_frames = lib().dvbt2ll_chain_unit_frames(self._h)
@@ -96,6 +101,56 @@ class Chain:
                                            (ctypes.c_int64 * n)(*[int(x) for x in ts_lens]), int(first_frame),
                                            int(nframes), ctypes.c_void_p(iq_ptr), ctypes.c_void_p(stream or None)),
               "chain run plps")
+
+    # ---- MISO pair handles (miso_pair=True): one IQ buffer per transmitter group; either pointer may be 0 / None
+    # (that group's OFDM launch is skipped)
+    def run_groups_device(self, ts_ptr, ts_stride, nstreams, ts_base, ts_len, first_frame, nframes, iq_ptrs, stream=0):
+        """as run_streams, into iq_ptrs = (group 1's buffer, group 2's) (dvbt2ll_chain_run_groups)"""
+        iq = (ctypes.c_void_p * 2)(*[ctypes.c_void_p(p or None) for p in iq_ptrs])
+        check(lib().dvbt2ll_chain_run_groups(self._h, ctypes.c_void_p(ts_ptr), int(ts_stride), int(nstreams),
+                                             int(ts_base), int(ts_len), int(first_frame), int(nframes), iq,
+                                             ctypes.c_void_p(stream or None)), "chain run groups")
+
+    def run_plps_groups(self, ts_ptrs, ts_bases, ts_lens, first_frame, nframes, iq_ptrs, stream=0):
+        """as run_plps, into iq_ptrs = (group 1's buffer, group 2's) (dvbt2ll_chain_run_plps_groups)"""
+        n = self.nplp
+        assert len(ts_ptrs) == len(ts_bases) == len(ts_lens) == n
+        iq = (ctypes.c_void_p * 2)(*[ctypes.c_void_p(p or None) for p in iq_ptrs])
+        check(lib().dvbt2ll_chain_run_plps_groups(self._h, (ctypes.c_void_p * n)(*ts_ptrs),
+                                                  (ctypes.c_int64 * n)(*[int(x) for x in ts_bases]),
+                                                  (ctypes.c_int64 * n)(*[int(x) for x in ts_lens]), int(first_frame),
+                                                  int(nframes), iq, ctypes.c_void_p(stream or None)),
+              "chain run plps groups")
+
+    def _groups_host(self, nframes, groups, launch):
+        """host convenience of the *_groups calls (torch holds the device buffers): launch(iq pointers, stream)
+        -> (iq1, iq2) numpy arrays, None for a group not asked for"""
+        import torch
+        sc16 = self.iq_format == IQ_SC16
+        bufs = [torch.empty((nframes * self.iq_per_frame, 2), dtype=torch.int16 if sc16 else torch.float32,
+                            device="cuda") if g else None for g in groups]
+        launch([b.data_ptr() if b is not None else 0 for b in bufs], torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return tuple(None if b is None else (b.cpu().numpy() if sc16 else
+                                             b.cpu().numpy().view(np.complex64).reshape(-1)) for b in bufs)
+
+    def run_groups(self, first_frame, nframes, ts=None, ts_base=None, seed=1, groups=(True, True)):
+        """host convenience (single-PLP pair handle): synthetic TS (or the given buffer) -> (iq1, iq2), group 1's
+        and group 2's IQ as numpy arrays"""
+        import torch
+        if ts is None:
+            ts, ts_base = ts_for_frames(self.cfg, first_frame, nframes, seed)
+        ts_d = torch.from_numpy(np.ascontiguousarray(ts, np.uint8)).cuda()
+        return self._groups_host(nframes, groups, lambda iq, st: self.run_groups_device(
+            ts_d.data_ptr(), 0, 1, ts_base, ts_d.numel(), first_frame, nframes, iq, st))
+
+    def run_plps_groups_host(self, ts, ts_bases, first_frame, nframes, groups=(True, True)):
+        """host convenience (multi-PLP pair handle): ts[k] PLP k's TS bytes at absolute offset ts_bases[k]
+        -> (iq1, iq2)"""
+        import torch
+        ts_d = [torch.from_numpy(np.ascontiguousarray(t, np.uint8)).cuda() for t in ts]
+        return self._groups_host(nframes, groups, lambda iq, st: self.run_plps_groups(
+            [t.data_ptr() for t in ts_d], ts_bases, [t.numel() for t in ts_d], first_frame, nframes, iq, st))
 
     def debug_plp_codewords(self, plp, nblocks):
         stride = self.plp_info[plp]["cw_stride_bytes"]

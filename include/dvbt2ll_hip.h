@@ -376,6 +376,33 @@ int dvbt2ll_chain_run_plps_host(dvbt2ll_chain *h, const void *const *ts, const i
 int dvbt2ll_chain_debug_plp_codewords(dvbt2ll_chain *h, int plp, void *out, int64_t bytes);
 
 /* ---------------------------------------------------------------------------
+ * MISO pair chain: both transmitter groups of one MISO service from one FEC + map pass.  A pair handle encodes
+ * each frame once (one BB + BCH launch and one LDPC + map launch per PLP, with the L1-post workgroups) and runs
+ * two OFDM launches over the same index-pair buffer and L1-post cells: group 1's output is bit-identical to a
+ * MISO_TX1 handle's, group 2's to a DVBT2LL_MISO_TX2_PROCESSED handle's.  The pair buffer is in group 1's slot
+ * order; group 2's launch reads it through tables of its own and is not bank-balanced for its own bins.
+ * p->misogroup must be MISO_TX1 (0) and the preamble a MISO one, else DVBT2LL_EINVAL.
+ * On a pair handle set_output, set_slots, set_timing (stage 2 accumulates both OFDM launches), sync_errors (each
+ * packet counted once), get_info and the debug hooks (dvbt2ll_chain_debug_cell_pairs / _cells: group 1's slot
+ * order) work as on any chain; a buffer slot reused on another stream waits for both OFDM launches of its
+ * previous run.  Not supported on a pair handle, DVBT2LL_EINVAL with nothing launched: the single-output run
+ * calls (run_device, run_streams, run_plps, the host and streaming-host calls) and set_graph(1): graph mode and
+ * the streaming host ring are out of scope for pair handles.
+ * ------------------------------------------------------------------------- */
+int dvbt2ll_chain_create_miso_pair(const dvbt2ll_chain_params *p, int device, dvbt2ll_chain **out);
+int dvbt2ll_chain_create_mplp_miso_pair(const dvbt2ll_mplp_chain_params *p, int device, dvbt2ll_chain **out);
+int dvbt2ll_chain_num_groups(const dvbt2ll_chain *h);   /* 2 for a pair handle, else 1 */
+/* as dvbt2ll_chain_run_streams (single-PLP) / dvbt2ll_chain_run_plps (multi-PLP), with one IQ buffer per group:
+ * iq_dev[0] = group 1 (a MISO_TX1 handle's output), iq_dev[1] = group 2 (a MISO_TX2_PROCESSED handle's), each
+ * laid out and aligned as run_streams' iq_dev.  One of the two may be NULL: that group's OFDM launch is skipped.
+ * DVBT2LL_EINVAL with nothing launched: an ordinary handle, both pointers NULL, a misaligned pointer. */
+int dvbt2ll_chain_run_groups(dvbt2ll_chain *h, const void *ts_dev, int64_t ts_stride, int nstreams, int64_t ts_base,
+                             int64_t ts_len, int64_t first_frame, int nframes, void *const iq_dev[2], void *stream);
+int dvbt2ll_chain_run_plps_groups(dvbt2ll_chain *h, const void *const *ts_dev, const int64_t *ts_base,
+                                  const int64_t *ts_len, int64_t first_frame, int nframes, void *const iq_dev[2],
+                                  void *stream);
+
+/* ---------------------------------------------------------------------------
  * ABI version.  The parameter and info structs are passed by pointer with no size field, so a caller
  * compiled against another layout would be read or written past its struct.  Version history:
  *   1  rounds 1-4: dvbt2ll_plp_params = the first nine ints, no num_subslices, no frames_per_if;
