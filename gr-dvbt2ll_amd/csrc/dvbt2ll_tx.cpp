@@ -7,6 +7,10 @@
 //
 //   dvbt2ll_tx --preset cfg3 --in stream.ts --out iq.sc16 --format sc16 --gain 0.2
 //   dvbt2ll_tx --mplp mix_4k --in plp0.ts --in plp1.ts --in plp2.ts --out iq.cf32
+//   dvbt2ll_tx --preset cfg3 --input bbframe --in frames.bbf --out iq.cf32
+//
+// --input bbframe reads a file of packed, unscrambled BBFRAMEs (kbch / 8 bytes each, back to back: what a T2
+// gateway built, e.g. the BBFRAME payloads of a T2-MI stream) in place of a TS (dvbt2ll_chain_set_input).
 //
 // --mplp runs a multi-PLP frame preset (one TS file per PLP, dvbt2ll_chain_create_mplp / _run_plps_host;
 // batches are whole launch units, dvbt2ll_chain_unit_frames).
@@ -77,6 +81,8 @@ void usage(FILE *f) {
                "                          inputmode reservedbiasbits l1scrambled inband; pilotgen:\n"
                "                          misogroup equalization bandwidth; bbheaderbch: tsrate)\n"
                "                          misogroup: 0 TX1, 1 TX2 (pilots only), 2 TX2 with MISO processing\n"
+               "  --input ts|bbframe      what --in holds: an MPEG-TS (default), or packed unscrambled BBFRAMEs\n"
+               "                          of kbch / 8 bytes each (single-PLP presets)\n"
                "  --format cf32|sc16      IQ sample format (default cf32, pilotgen's complex64)\n"
                "  --gain G                output gain (the flowgraph's multiply_const; default 1)\n"
                "  --frames N              T2 frames to encode (default: as many as the input holds)\n"
@@ -226,7 +232,7 @@ int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const st
 int main(int argc, char **argv) {
   std::string in_path, out_path, preset = "cfg1", mplp;
   std::vector<std::string> sets, ins;
-  int fmt = DVBT2LL_IQ_CF32, batch = 16, device = 0;
+  int fmt = DVBT2LL_IQ_CF32, input = DVBT2LL_INPUT_TS, batch = 16, device = 0;
   bool print_params = false;
   int64_t frames = -1;
   float gain = 1.f;
@@ -250,6 +256,11 @@ int main(int argc, char **argv) {
       if (v == "cf32") fmt = DVBT2LL_IQ_CF32;
       else if (v == "sc16") fmt = DVBT2LL_IQ_SC16;
       else { std::fprintf(stderr, "dvbt2ll_tx: unknown format %s\n", v.c_str()); return 2; }
+    } else if (a == "--input") {
+      std::string v = next();
+      if (v == "ts") input = DVBT2LL_INPUT_TS;
+      else if (v == "bbframe") input = DVBT2LL_INPUT_BBFRAME;
+      else { std::fprintf(stderr, "dvbt2ll_tx: unknown input %s\n", v.c_str()); return 2; }
     } else if (a == "--gain") gain = std::strtof(next(), nullptr);
     else if (a == "--frames") frames = std::strtoll(next(), nullptr, 10);
     else if (a == "--batch") batch = std::atoi(next());
@@ -259,6 +270,7 @@ int main(int argc, char **argv) {
   }
 
   if (!mplp.empty()) {
+    if (input != DVBT2LL_INPUT_TS) { std::fprintf(stderr, "dvbt2ll_tx: --input bbframe takes a single-PLP preset\n"); return 2; }
     for (auto &q : kMplpPresets)
       if (mplp == q.name) return run_mplp(q, ins, out_path, fmt, gain, frames, batch, device, print_params);
     std::fprintf(stderr, "dvbt2ll_tx: unknown multi-PLP preset %s\n", mplp.c_str());
@@ -294,7 +306,9 @@ int main(int argc, char **argv) {
   int st = dvbt2ll_chain_create(&p, device, &h);
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: chain create: %s\n", dvbt2ll_strerror(st)); return 1; }
   dvbt2ll_chain_info info;
-  if ((st = dvbt2ll_chain_get_info(h, &info)) || (st = dvbt2ll_chain_set_output(h, gain, fmt))) {
+  // (the info after set_input: it then counts whole BBFRAMEs)
+  if ((st = dvbt2ll_chain_set_input(h, -1, input)) || (st = dvbt2ll_chain_get_info(h, &info)) ||
+      (st = dvbt2ll_chain_set_output(h, gain, fmt))) {
     std::fprintf(stderr, "dvbt2ll_tx: %s\n", dvbt2ll_strerror(st));
     dvbt2ll_chain_destroy(h);
     return 1;
@@ -317,7 +331,21 @@ int main(int argc, char **argv) {
   // the ring: batch k's TS span and IQ in page-locked buffers of slot k % R until it is written out
   constexpr int R = DVBT2LL_HOST_RING;
   const size_t iq_slot = (size_t)batch * info.iq_samples_per_frame * sample_bytes;
-  const size_t ts_slot = (size_t)(payload_pos((int64_t)batch * pay_frame, hem) + 4 * 188);
+  const bool bbf = input == DVBT2LL_INPUT_BBFRAME;
+  // stream bytes [lo, end) the frames [first, first + n) consume: a TS span has the packet before the first one
+  // touched (its CRC-8 replaces the next sync byte); BBFRAME input: the frames' BBFRAMEs and nothing else
+  auto span_of = [&](int64_t first, int64_t n, int64_t *lo, int64_t *end) {
+    if (bbf) {
+      *lo = first * info.ts_bytes_per_frame;
+      *end = (first + n) * info.ts_bytes_per_frame;
+      return;
+    }
+    const int64_t start = payload_pos(first * pay_frame, hem);
+    *end = payload_pos((first + n) * pay_frame, hem) + 1;
+    *lo = start >= 188 ? (start / 188) * 188 - 188 : 0;
+  };
+  const size_t ts_slot = bbf ? (size_t)((int64_t)batch * info.ts_bytes_per_frame)
+                             : (size_t)(payload_pos((int64_t)batch * pay_frame, hem) + 4 * 188);
   void *ts_pin[R] = {}, *iq_pin[R] = {};
   int64_t ticket[R] = {}, slot_frames[R] = {};
   for (int k = 0; k < R; k++)
@@ -344,11 +372,8 @@ int main(int argc, char **argv) {
   while (!st && (frames < 0 || done < frames)) {
     int n = batch;
     if (frames >= 0 && frames - done < n) n = (int)(frames - done);
-    // stream bytes the frames [done, done + n) consume, plus the packet before the first
-    // (its CRC-8 replaces the next sync byte): [lo, end)
-    const int64_t start = payload_pos(done * pay_frame, hem);
-    int64_t end = payload_pos((done + n) * pay_frame, hem) + 1;
-    const int64_t lo = start >= 188 ? (start / 188) * 188 - 188 : 0;
+    int64_t lo, end;
+    span_of(done, n, &lo, &end);
     if (lo > ts_base) {                    // drop bytes no later frame needs
       ts.erase(ts.begin(), ts.begin() + (lo - ts_base));
       ts_base = lo;
@@ -362,7 +387,7 @@ int main(int argc, char **argv) {
     }
     while (n > 0 && ts_base + (int64_t)ts.size() < end) {   // short input: fewer frames
       n--;
-      end = payload_pos((done + n) * pay_frame, hem) + 1;
+      span_of(done, n, &lo, &end);
     }
     if (n == 0) break;
     if (submitted - written == R && !drain_one()) break;   // the slot's previous batch goes out first

@@ -696,6 +696,12 @@ struct ChainPlp {
                               // interleaving frame
   int cyc = 1;                // T2 frames from one interleaving frame to the next (P_I x FRAME_INTERVAL)
   int64_t blocks(int64_t frames) const { return (frames + cyc - 1) / cyc * F; }   // FEC blocks of `frames` T2 frames
+  // what the run calls' input holds (dvbt2ll_chain_set_input): the TS, or packed BBFRAMEs of bbf_len() bytes,
+  // interleaving frame m consuming stream bytes [m F bbf_len(), (m + 1) F bbf_len())
+  int input = DVBT2LL_INPUT_TS;
+  int64_t bbf_len() const { return fec.plan.kbch / 8; }
+  // the unit the run calls' ts_base must be a multiple of
+  int64_t base_unit() const { return input == DVBT2LL_INPUT_BBFRAME ? bbf_len() : 188; }
 };
 
 // instantiated hipGraphs of the chain's kernels (per PLP: bbch_kernel, BBFRAMEs + matrix-core BCH; per PLP: LDPC +
@@ -792,6 +798,7 @@ struct dvbt2ll_chain {
   std::vector<int32_t> plp_bnd_host;
   std::vector<int> qbase_host;
   DevBuf sync_err;                      // TS sync bytes != 0x47 consumed by run calls (bbheader:675, 703)
+  DevBuf bbh_err;                       // BBFRAME input: BBFRAMEs consumed whose header CRC-8 does not match
   // intermediate buffer slots (index pairs, L1-post cells; the PLPs' codewords): run calls take them
   // round-robin, so calls issued on different streams overlap; a slot reused on another stream first
   // waits for its previous run (slot_done) -- see dvbt2ll_chain_set_slots
@@ -1269,8 +1276,9 @@ static int chain_build(dvbt2ll_chain *h, const FmParams &fm, const std::vector<P
     return DVBT2LL_EINVAL;
   if ((r = h->alloc_slot(0))) return r;
   if ((r = upload(h->aux, auxv))) return r;
-  if (h->sync_err.ensure(4)) return DVBT2LL_ENOMEM;
+  if (h->sync_err.ensure(4) || h->bbh_err.ensure(4)) return DVBT2LL_ENOMEM;
   HIP_TRY(hipMemset(h->sync_err.p, 0, 4));
+  HIP_TRY(hipMemset(h->bbh_err.p, 0, 4));
   return 0;
 }
 
@@ -1350,6 +1358,10 @@ extern "C" int dvbt2ll_chain_get_plp_info(const dvbt2ll_chain *h, int plp, dvbt2
   info->fec_blocks_per_frame = pl.F;
   info->payload_bytes_per_block = pl.pay;
   info->ts_bytes_per_frame = pl.inputmode ? (pl.ts_per_frame * 188 + 186) / 187 : pl.ts_per_frame;
+  if (pl.input == DVBT2LL_INPUT_BBFRAME) {   // whole BBFRAMEs, header included
+    info->payload_bytes_per_block = (int)pl.bbf_len();
+    info->ts_bytes_per_frame = pl.F * pl.bbf_len();
+  }
   info->iq_samples_per_frame = h->iq_per_frame;
   info->cell_size = h->frame.plp[plp].cs;
   info->stream_items = h->frame.plp[plp].S;
@@ -1375,8 +1387,14 @@ extern "C" int dvbt2ll_chain_run_device(dvbt2ll_chain *h, const void *ts_dev, in
 }
 
 // stream bytes [lo, end) that frames [first, first + n) of PLP pl consume: their payload plus the packet before
-// the first one touched (its CRC-8 replaces the next sync byte, bbheader:701-713)
+// the first one touched (its CRC-8 replaces the next sync byte, bbheader:701-713).  BBFRAME input: exactly the
+// frames' BBFRAMEs, no byte before them
 static void ts_span(const ChainPlp &pl, int64_t first, int64_t n, int64_t *lo, int64_t *end) {
+  if (pl.input == DVBT2LL_INPUT_BBFRAME) {
+    *lo = first / pl.cyc * pl.F * pl.bbf_len();
+    *end = (first + n) / pl.cyc * pl.F * pl.bbf_len();
+    return;
+  }
   int64_t start = first / pl.cyc * pl.ts_per_frame, e = (first + n) / pl.cyc * pl.ts_per_frame;
   if (pl.inputmode) {
     start = 188 * (start / 187) + (start % 187);
@@ -1384,6 +1402,15 @@ static void ts_span(const ChainPlp &pl, int64_t first, int64_t n, int64_t *lo, i
   }
   *lo = start >= 188 ? (start / 188) * 188 - 188 : 0;
   *end = e;
+}
+
+// BBFRAME input from host memory: the span [lo, end) of the frames' BBFRAMEs (the host paths copy exactly those
+// bytes), nonzero when the caller's [base, base + len) does not hold it or base is no BBFRAME boundary
+static int bbf_host_span(const ChainPlp &pl, int64_t base, int64_t len, int64_t first, int64_t n, int64_t *lo,
+                         int64_t *end) {
+  if (first < 0 || n < 1 || base < 0 || len < 0 || base % pl.base_unit()) return DVBT2LL_EINVAL;
+  ts_span(pl, first, n, lo, end);
+  return base > *lo || base + len < *end ? DVBT2LL_EINVAL : 0;
 }
 
 // one run over nstreams independent single-PLP streams (nplp == 1) or over one frame sequence of
@@ -1406,8 +1433,9 @@ static int chain_run(dvbt2ll_chain *h, const void *const *ts, const int64_t *bas
   hipStream_t s = stream ? (hipStream_t)stream : h->ctx.stream;
   for (int k = 0; k < h->nplp; k++) {
     const ChainPlp &pl = *h->plps[k];
-    if (!ts[k] || base[k] < 0 || base[k] % 188 != 0) return DVBT2LL_EINVAL;
-    // the TS slice must cover every byte the frames consume plus the packet before the first one touched
+    if (!ts[k] || base[k] < 0 || base[k] % pl.base_unit() != 0) return DVBT2LL_EINVAL;
+    // the TS slice must cover every byte the frames consume plus the packet before the first one touched (BBFRAME
+    // input: the frames' BBFRAMEs)
     int64_t lo, end;
     ts_span(pl, first_frame, nframes, &lo, &end);
     if (base[k] > lo || base[k] + len[k] < end) return DVBT2LL_EINVAL;
@@ -1449,6 +1477,7 @@ static int chain_run(dvbt2ll_chain *h, const void *const *ts, const int64_t *bas
     fio[k].cw_stride = pl.cw_stride;
     fio[k].nblocks = (int)pl.blocks(nf);
     fio[k].sync_err = h->sync_err.as<uint32_t>();
+    fio[k].bbh_err = h->bbh_err.as<uint32_t>();
     fio[k].blocks_per_stream = nstreams > 1 ? (int)pl.blocks(nframes) : 0;
     fio[k].ts_stride = nstreams > 1 ? ts_stride : 0;
     fio[k].bch_part = pl.bpart[slot].as<uint32_t>();
@@ -1560,6 +1589,13 @@ extern "C" int dvbt2ll_chain_run_host(dvbt2ll_chain *h, const void *ts, int64_t 
   if (!h || !ts || !iq || nframes < 1 || nframes > h->max_frames || h->nplp != 1 || h->pair) return DVBT2LL_EINVAL;
   HIP_TRY(hipSetDevice(h->ctx.device));
   size_t iq_bytes = (size_t)nframes * h->iq_per_frame * (h->ofdm.dev.fmt == DVBT2LL_IQ_SC16 ? 4 : 8);
+  if (h->plps[0]->input == DVBT2LL_INPUT_BBFRAME) {   // exactly the frames' BBFRAMEs go to the device
+    int64_t lo, end;
+    if (bbf_host_span(*h->plps[0], ts_base, ts_len, first_frame, nframes, &lo, &end)) return DVBT2LL_EINVAL;
+    ts = (const uint8_t *)ts + (lo - ts_base);
+    ts_base = lo;
+    ts_len = end - lo;
+  }
   if (h->ts_tmp.ensure((size_t)ts_len + 16) || h->iq_tmp.ensure(iq_bytes)) return DVBT2LL_ENOMEM;
   HIP_TRY(hipMemcpyAsync(h->ts_tmp.p, ts, (size_t)ts_len, hipMemcpyHostToDevice, h->ctx.stream));
   int r = dvbt2ll_chain_run_device(h, h->ts_tmp.p, ts_base, ts_len, first_frame, nframes, h->iq_tmp.p, nullptr);
@@ -1575,15 +1611,26 @@ extern "C" int dvbt2ll_chain_run_plps_host(dvbt2ll_chain *h, const void *const *
     return DVBT2LL_EINVAL;
   HIP_TRY(hipSetDevice(h->ctx.device));
   const void *dev[DVBT2LL_MAX_PLP];
+  int64_t base[DVBT2LL_MAX_PLP], len[DVBT2LL_MAX_PLP];
   for (int k = 0; k < h->nplp; k++) {
     if (!ts[k] || ts_len[k] < 0) return DVBT2LL_EINVAL;
-    if (h->ts_plp_tmp[k].ensure((size_t)ts_len[k] + 16)) return DVBT2LL_ENOMEM;
-    HIP_TRY(hipMemcpyAsync(h->ts_plp_tmp[k].p, ts[k], (size_t)ts_len[k], hipMemcpyHostToDevice, h->ctx.stream));
+    const uint8_t *src = (const uint8_t *)ts[k];
+    base[k] = ts_base[k];
+    len[k] = ts_len[k];
+    if (h->plps[k]->input == DVBT2LL_INPUT_BBFRAME) {   // exactly the frames' BBFRAMEs go to the device
+      int64_t lo, end;
+      if (bbf_host_span(*h->plps[k], ts_base[k], ts_len[k], first_frame, nframes, &lo, &end)) return DVBT2LL_EINVAL;
+      src += lo - ts_base[k];
+      base[k] = lo;
+      len[k] = end - lo;
+    }
+    if (h->ts_plp_tmp[k].ensure((size_t)len[k] + 16)) return DVBT2LL_ENOMEM;
+    HIP_TRY(hipMemcpyAsync(h->ts_plp_tmp[k].p, src, (size_t)len[k], hipMemcpyHostToDevice, h->ctx.stream));
     dev[k] = h->ts_plp_tmp[k].p;
   }
   const size_t iq_bytes = (size_t)nframes * h->iq_per_frame * (h->ofdm.dev.fmt == DVBT2LL_IQ_SC16 ? 4 : 8);
   if (h->iq_tmp.ensure(iq_bytes)) return DVBT2LL_ENOMEM;
-  int r = dvbt2ll_chain_run_plps(h, dev, ts_base, ts_len, first_frame, nframes, h->iq_tmp.p, nullptr);
+  int r = dvbt2ll_chain_run_plps(h, dev, base, len, first_frame, nframes, h->iq_tmp.p, nullptr);
   if (r) return r;
   HIP_TRY(hipMemcpyAsync(iq, h->iq_tmp.p, iq_bytes, hipMemcpyDeviceToHost, h->ctx.stream));
   HIP_TRY(hipStreamSynchronize(h->ctx.stream));
@@ -1595,7 +1642,7 @@ extern "C" int dvbt2ll_chain_host_submit(dvbt2ll_chain *h, const void *ts, int64
   // every argument check precedes the first asynchronous operation, so a refused submission leaves no copy
   // of the caller's buffers in flight (the unit check is repeated by chain_run, after the copy-in is queued)
   if (!h || !ts || !iq || !ticket || h->nplp != 1 || h->pair || nframes < 1 || nframes > h->max_frames || first_frame < 0 ||
-      ts_base < 0 || ts_base % 188 || first_frame % h->frame.unit || nframes % h->frame.unit)
+      ts_base < 0 || ts_base % h->plps[0]->base_unit() || first_frame % h->frame.unit || nframes % h->frame.unit)
     return DVBT2LL_EINVAL;
   const ChainPlp &pl = *h->plps[0];
   int64_t lo, end;
@@ -1647,7 +1694,7 @@ extern "C" int dvbt2ll_chain_run_host_pipelined(dvbt2ll_chain *h, const void *ts
   // chunks of whole launch units; every chunk is checked before the first one is submitted
   int c = chunk_frames ? std::min(chunk_frames, h->max_frames) : h->max_frames;
   c -= c % U;
-  if (c < U || first_frame < 0 || first_frame % U || nframes % U || ts_base < 0 || ts_base % 188)
+  if (c < U || first_frame < 0 || first_frame % U || nframes % U || ts_base < 0 || ts_base % h->plps[0]->base_unit())
     return DVBT2LL_EINVAL;
   {
     int64_t lo, end;
@@ -1692,6 +1739,34 @@ extern "C" int dvbt2ll_chain_set_output(dvbt2ll_chain *h, float gain, int format
   h->ofdm.dev.fmt = format;
   h->ofdm2.dev.gain = gain;   // (a pair handle's group 2)
   h->ofdm2.dev.fmt = format;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_chain_set_input(dvbt2ll_chain *h, int plp, int format) {
+  if (!h || plp < -1 || plp >= h->nplp || (format != DVBT2LL_INPUT_TS && format != DVBT2LL_INPUT_BBFRAME))
+    return DVBT2LL_EINVAL;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  HIP_TRY(hipDeviceSynchronize());   // no run in flight while the format changes
+  for (int k = 0; k < h->nplp; k++) {
+    if (plp >= 0 && k != plp) continue;
+    h->plps[k]->input = format;
+    h->plps[k]->fec.dev.input = format == DVBT2LL_INPUT_BBFRAME ? FEC_INPUT_BBFRAME : FEC_INPUT_TS;
+  }
+  // the instantiated graphs hold the other format's kernel in their first nodes: the next graph run captures anew
+  h->graphs.clear();
+  return DVBT2LL_OK;
+}
+extern "C" int dvbt2ll_chain_get_input(const dvbt2ll_chain *h, int plp) {
+  if (!h || plp < 0 || plp >= h->nplp) return DVBT2LL_EINVAL;
+  return h->plps[plp]->input;
+}
+extern "C" int dvbt2ll_chain_bbheader_errors(dvbt2ll_chain *h, int64_t *count) {
+  if (!h || !count) return DVBT2LL_EINVAL;
+  uint32_t v = 0;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(&v, h->bbh_err.p, 4, hipMemcpyDeviceToHost));
+  *count = (int64_t)v;
   return DVBT2LL_OK;
 }
 

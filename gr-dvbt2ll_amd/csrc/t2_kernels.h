@@ -36,8 +36,13 @@ struct FecDev {
   // BBHEADER MATYPE-1 << 8 | MATYPE-2: 0xF000 = TS, SIS, CCM, ISSYI 0, NPD 0, RO 0, ISI 0 (the reference's
   // ctor, bbheader:168-182); 0xD000 | ISI = multiple input streams (one PLP of a multi-PLP frame, :288-298)
   int matype;
+  // chain: what FecIO::in holds (FEC_INPUT_*).  BBFRAME input: packed, unscrambled BBFRAMEs of kbch / 8 bytes back
+  // to back; the chain scrambles them and appends the BCH parity, and writes no header, padding or in-band field
+  // (hem, inband, ts_rate and matype are then unused by the fused pass)
+  int input;
 };
 constexpr int MATYPE_SIS = 0xF000, MATYPE_MIS = 0xD000;
+constexpr int FEC_INPUT_TS = 0, FEC_INPUT_BBFRAME = 1;
 
 struct FecIO {
   const uint8_t *in;       // TS bytes (ts modes) or unpacked bits
@@ -60,6 +65,9 @@ struct FecIO {
   // launch_ldpc_map (test hook): 1 = also store each block's interleaver-input codeword into its row
   // (the BBFRAME already there), 0 = the codeword stays in LDS
   int keep_cw;
+  // chain, BBFRAME input, optional: += BBFRAMEs whose header byte 9 is neither the CRC-8 of bytes 0 .. 8 nor that
+  // value XOR 1 (the HEM mode bit), each counted once per launch
+  uint32_t *bbh_err;
 };
 
 // ---------------------------------------------------------------- L1-post signalling (t2_plan.h L1PostPlan)

@@ -816,9 +816,17 @@ __device__ __forceinline__ uint32_t crc_chunk(const uint8_t *tp, const uint8_t *
   return h ? o1 : z;
 }
 
-template <int NT, bool HEM>
+// What the rows are built from: the TS in normal mode or high-efficiency mode (above), or BBFRAMEs the caller built
+// (FEC_INPUT_BBFRAME): the piece is then input bytes [B L + P0, + 16) of the block's stream (B the absolute block
+// index, L = kbch / 8), masked to zero from BBFRAME byte L on and scrambled.  No header, padding or in-band field
+// is written, there is no CRC stream and so no prologue; the header's own CRC-8 (byte 9 over bytes 0 .. 8, or that
+// value with the HEM mode bit, XOR 1) is checked where chunk 0 is built and counted in io.bbh_err.
+enum BbchInput { BBCH_NM = 0, BBCH_HEM = 1, BBCH_BBF = 2 };
+
+template <int NT, int KIND>
 __global__ __launch_bounds__(BBCH_THREADS, BBCH_WG_PER_CU) void bbch_kernel(FecDev d, FecIO io) {
   extern __shared__ __attribute__((aligned(16))) uint4 bsm[];
+  constexpr bool HEM = KIND == BBCH_HEM, BBF = KIND == BBCH_BBF;
   constexpr int PER = 4 * NT * 64;                   // uint4 per chunk buffer
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
   const int L = d.kbch >> 3;
@@ -829,7 +837,7 @@ __global__ __launch_bounds__(BBCH_THREADS, BBCH_WG_PER_CU) void bbch_kernel(FecD
   // ---- tables, once per workgroup: T^1..T^16 and their inverses (NM), the BBHEADER CRC-8 per header byte
   // (add_crc8_bits :247-270: XOR of the per-bit contributions hcrc_bits, bit 8 b + j = bit 7 - j of byte b), the
   // in-band type B bytes (:327-355: 01, 65 zero bits, the TS rate in 27 bits, 10 zero bits)
-  if (!HEM && tid < 256) {   // (BBCH_THREADS >= 256)
+  if (!HEM && !BBF && tid < 256) {   // (BBCH_THREADS >= 256)
     uint32_t v = (uint32_t)tid;
     for (int k = 0; k < 16; k++) {
       v = d.crc8_tab[v];
@@ -843,11 +851,11 @@ __global__ __launch_bounds__(BBCH_THREADS, BBCH_WG_PER_CU) void bbch_kernel(FecD
       if ((x >> (7 - j)) & 1) v ^= d.hcrc_bits[8 * b + j];
     hd[i] = (uint8_t)v;
   }
-  if (tid < 17 * 4) {   // prefix masks
+  if (!BBF && tid < 17 * 4) {   // prefix masks
     const int e = tid >> 2, k = tid & 3, n = min(max(e + 1 - 4 * k, 0), 4);
     ((uint32_t *)pmask)[tid] = n >= 4 ? 0xFFFFFFFFu : (1u << (8 * n)) - 1u;
   }
-  if (tid < 13) {   // = inband_byte(tid, d.ts_rate), written out: calling it here changes this kernel's code
+  if (!BBF && tid < 13) {   // = inband_byte(tid, d.ts_rate), written out: calling it here changes this kernel's code
     uint32_t v = tid == 0 ? 0x40u : 0u;
     for (int e = 0; e < 8; e++) {
       const int bit = 8 * tid + e;
@@ -856,7 +864,7 @@ __global__ __launch_bounds__(BBCH_THREADS, BBCH_WG_PER_CU) void bbch_kernel(FecD
     ibb[tid] = (uint8_t)v;
   }
   __syncthreads();
-  if (!HEM && tid < 256)
+  if (!HEM && !BBF && tid < 256)
     for (int k = 0; k < 16; k++) tq[k * 256 + tp[k * 256 + tid]] = (uint8_t)tid;
   __syncthreads();
 
@@ -902,15 +910,20 @@ __global__ __launch_bounds__(BBCH_THREADS, BBCH_WG_PER_CU) void bbch_kernel(FecD
     BbchRow R{};
     R.live = blk < io.nblocks;
     R.tin = io.in;
+    int64_t B = 0;
     if (R.live) {
-      const int64_t B = fec_block_of(io, blk, R.tin);
-      R.g = bb_geom(d, io, B);
+      B = fec_block_of(io, blk, R.tin);
+      if (!BBF) R.g = bb_geom(d, io, B);
     }
     R.row = io.out + (int64_t)(R.live ? blk : 0) * io.cw_stride;
     const int npay = R.g.npay;
     uint32_t crc = 0;   // NM: the CRC register at the start of this lane's row's current chunk (both lanes)
     // ---- per-lane cursors at the first chunk this segment streams
-    if (!HEM) {
+    if (BBF) {
+      // input offset of this lane's piece of chunk q0 (a dead row: block 0's, loaded or not as the buffer allows,
+      // never used)
+      R.rel = B * L - io.ts_base + 32 * q0 + 16 * h;
+    } else if (!HEM) {
       const int qa = q0 - BBCH_PRO;
       const int64_t S = R.g.pos0 + 32 * qa + 16 * h - 10;   // >= pos0 - 208
       R.rel = S - io.ts_base;
@@ -939,6 +952,27 @@ __global__ __launch_bounds__(BBCH_THREADS, BBCH_WG_PER_CU) void bbch_kernel(FecD
     // ---- the piece of chunk q in four dwords; stores nothing
     auto build = [&](int q, TsWin w, uint32_t *pd) {
       const int P0 = 32 * q + 16 * h;
+      if (BBF) {
+        if (w.edge && R.live && P0 < L) ts_slow(R.tin, io.ts_len, R.rel, w);
+        // the header's CRC-8 from the per-byte tables, as the TS kinds compute the one they write (below); chunk 0
+        // of a row is built by one segment of one slice, so a BBFRAME is counted once per launch
+        if (P0 == 0 && R.live && io.bbh_err) {
+          uint32_t c = 0;
+#pragma unroll
+          for (int b = 0; b < 9; b++) c ^= hd[b * 256 + ((w.a[b >> 2] >> (8 * (b & 3))) & 0xFFu)];
+          if ((((__builtin_bitreverse32(c) >> 24) ^ (w.a[2] >> 8)) & 0xFEu) != 0u) atomicAdd(io.bbh_err, 1u);
+        }
+        // bytes from BBFRAME byte L on (the next BBFRAME's, or whatever the safe address held) are zero; the PRBS
+        // padding is zero there too
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int t = min(max(L - P0 - 4 * k, 0), 4);
+          const uint32_t m = t >= 4 ? 0xFFFFFFFFu : (1u << (8 * t)) - 1u;   // bytes i < L - P0
+          pd[k] = (w.a[k] & m) ^ w.p[k];
+        }
+        R.rel += 32;
+        return;
+      }
       if (w.edge && R.live && P0 < L && P0 - 10 < npay && (P0 >= 10 || !HEM))
         ts_slow(R.tin, io.ts_len, HEM ? R.sh - io.ts_base : R.rel, w);
       uint32_t raw[4];
@@ -1234,7 +1268,9 @@ static hipError_t fec_launch_persistent(const void *fn, int kind, int cap, const
 template <int NT>
 static hipError_t bbch_launch(const FecDev &d, const FecIO &io, hipStream_t s) {
   const int lds = bbch_lds(NT);
-  const void *fn = d.hem ? (const void *)bbch_kernel<NT, true> : (const void *)bbch_kernel<NT, false>;
+  const void *fn = d.input == FEC_INPUT_BBFRAME ? (const void *)bbch_kernel<NT, BBCH_BBF>
+                   : d.hem                      ? (const void *)bbch_kernel<NT, BBCH_HEM>
+                                                : (const void *)bbch_kernel<NT, BBCH_NM>;
   hipError_t e = lds_limit(fn, lds);
   if (e != hipSuccess) return e;
   // persistent: BBCH_WG_PER_CU workgroups per CU, a multiple of BCH_KS (slices by XCD)
@@ -1245,7 +1281,7 @@ static hipError_t bbch_launch(const FecDev &d, const FecIO &io, hipStream_t s) {
 
 static bool fec_chain_args_ok(const FecDev &d, const FecIO &io) {
   return d.bch_mfma && io.bch_part && io.bch_part_blocks >= io.nblocks && d.bch_nt >= 4 && d.bch_nt <= 6 && io.ts_len >= 64 &&
-         d.bch_nq >= 1 && d.bch_nq * 32 <= io.cw_stride;
+         d.bch_nq >= 1 && d.bch_nq * 32 <= io.cw_stride && (d.input == FEC_INPUT_TS || d.input == FEC_INPUT_BBFRAME);
 }
 
 hipError_t launch_fec(int mode, const FecDev &d, const FecIO &io, hipStream_t s) {

@@ -108,6 +108,7 @@ EXPORTS += ["dvbt2ll_chain_" + f for f in ("create_mplp", "num_plps", "unit_fram
                                            "debug_plp_codewords", "debug_keep_codewords")]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create_miso_pair", "create_mplp_miso_pair", "num_groups", "run_groups",
                                            "run_plps_groups")]
+EXPORTS += ["dvbt2ll_chain_" + f for f in ("set_input", "get_input", "bbheader_errors")]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create", "get_info", "run_device", "run_streams", "run_host", "set_output", "set_slots", "set_graph", "set_timing",
                                            "get_timing", "debug_codewords", "debug_cell_pairs", "debug_cells",
                                            "synchronize", "sync_errors",
@@ -192,6 +193,9 @@ def lib():
     L.dvbt2ll_chain_run_groups.argtypes = [vp, vp, i64, ci, i64, i64, i64, ci, ctypes.POINTER(vp), vp]
     L.dvbt2ll_chain_run_plps_groups.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64), i64,
                                                 ci, ctypes.POINTER(vp), vp]
+    L.dvbt2ll_chain_set_input.argtypes = [vp, ci, ci]
+    L.dvbt2ll_chain_get_input.argtypes = [vp, ci]
+    L.dvbt2ll_chain_bbheader_errors.argtypes = [vp, ctypes.POINTER(i64)]
     L.dvbt2ll_chain_destroy.argtypes = [vp]
     L.dvbt2ll_chain_destroy.restype = None
     _lib = L

@@ -15,6 +15,8 @@ from .configs import MISO_TX2_PROCESSED  # noqa: F401  (a cfg.misogroup value th
 
 IQ_CF32 = 0   # DVBT2LL_IQ_CF32
 IQ_SC16 = 1   # DVBT2LL_IQ_SC16
+INPUT_TS = 0        # DVBT2LL_INPUT_TS
+INPUT_BBFRAME = 1   # DVBT2LL_INPUT_BBFRAME
 
 
 class Chain:
@@ -43,13 +45,7 @@ class Chain:
         self.nplp = lib().dvbt2ll_chain_num_plps(self._h)
         # runs cover whole interleaving frames: first_frame and nframes multiples of unit_frames
         self.unit_frames = lib().dvbt2ll_chain_unit_frames(self._h)
-        info = _ChainInfo()
-        check(lib().dvbt2ll_chain_get_info(self._h, ctypes.byref(info)), "chain info")
-        self.info = {f: getattr(info, f) for f, _ in _ChainInfo._fields_}
-        self.plp_info = []
-        for k in range(self.nplp):
-            check(lib().dvbt2ll_chain_get_plp_info(self._h, k, ctypes.byref(info)), "plp info")
-            self.plp_info.append({f: getattr(info, f) for f, _ in _ChainInfo._fields_})
+        self._read_info()
         self.iq_format = IQ_CF32
         self.nslots = 1
 
@@ -58,6 +54,31 @@ class Chain:
         (complex64, pilotgen's own output) or IQ_SC16 (int16 I/Q pairs, full scale 32767)"""
         check(lib().dvbt2ll_chain_set_output(self._h, float(gain), int(fmt)), "chain output")
         self.iq_format = int(fmt)
+
+    def _read_info(self):
+        info = _ChainInfo()
+        check(lib().dvbt2ll_chain_get_info(self._h, ctypes.byref(info)), "chain info")
+        self.info = {f: getattr(info, f) for f, _ in _ChainInfo._fields_}
+        self.plp_info = []
+        for k in range(self.nplp):
+            check(lib().dvbt2ll_chain_get_plp_info(self._h, k, ctypes.byref(info)), "plp info")
+            self.plp_info.append({f: getattr(info, f) for f, _ in _ChainInfo._fields_})
+
+    def set_input(self, fmt, plp=-1):
+        """input format of PLP plp (-1: every PLP) for the following run calls: INPUT_TS, or INPUT_BBFRAME --
+        packed, unscrambled BBFRAMEs of kbch / 8 bytes each, which the chain scrambles, BCH-encodes and carries on
+        with (dvbt2ll_chain_set_input).  info / plp_info then count BBFRAME bytes"""
+        check(lib().dvbt2ll_chain_set_input(self._h, int(plp), int(fmt)), "chain input")
+        self._read_info()
+
+    def get_input(self, plp=0):
+        return check(lib().dvbt2ll_chain_get_input(self._h, int(plp)), "chain input")
+
+    def bbheader_errors(self):
+        """BBFRAME input: BBFRAMEs consumed so far whose header CRC-8 matches neither mode; synchronises the device"""
+        n = ctypes.c_int64(0)
+        check(lib().dvbt2ll_chain_bbheader_errors(self._h, ctypes.byref(n)), "bbheader errors")
+        return n.value
 
     def set_slots(self, nslots):
         """intermediate buffer slots taken round-robin by run calls: with nslots > 1, calls
@@ -160,8 +181,11 @@ class Chain:
         return out.reshape(nblocks, stride)
 
     def run(self, first_frame, nframes, ts=None, ts_base=None, seed=1):
-        """host convenience: synthetic TS (or the given buffer) -> IQ numpy array"""
+        """host convenience: synthetic TS (or the given buffer) -> IQ numpy array.  A handle in INPUT_BBFRAME format
+        takes ts = a BBFRAME byte array whose byte 0 is stream offset ts_base (configs.bbframe_span)"""
         if ts is None:
+            if self.get_input(0) != INPUT_TS:
+                raise ValueError("a handle in BBFRAME format has no synthetic input: pass the BBFRAME bytes and ts_base")
             ts, ts_base = ts_for_frames(self.cfg, first_frame, nframes, seed)
         ts = np.ascontiguousarray(ts, np.uint8)
         if self.iq_format == IQ_SC16:   # interleaved int16 I, Q

@@ -275,6 +275,21 @@ def ts_for_frames(cfg, first_frame, nframes, seed=1):
     return ts_packets(p0, p1 - p0, seed), p0 * 188
 
 
+def bbframe_bytes(cfg):
+    """bytes of one BBFRAME (kbch / 8: the 10 header bytes and the data field)"""
+    return KBCH[(cfg.framesize, cfg.rate)] // 8
+
+
+def bbframe_span(cfg, first_frame, nframes):
+    """BBFRAME input (Chain.set_input(INPUT_BBFRAME)): the bytes [lo, end) of the PLP's packed BBFRAME stream that
+    T2 frames [first_frame, first_frame + nframes) consume, the C library's own check: interleaving frame m (one
+    T2 frame, or if_frames of them) takes FEC blocks [m F, (m + 1) F), bytes [m F L, (m + 1) F L), L = kbch / 8,
+    and nothing before them.  A run's ts_base is a multiple of L, at most lo, and its buffer reaches end."""
+    P = getattr(cfg, "if_frames", 1)
+    per_if = cfg.fecblocks * bbframe_bytes(cfg)
+    return first_frame // P * per_if, (first_frame + nframes) // P * per_if
+
+
 def _mplp_configs():
     c3, c1, c4 = CONFIGS["cfg3"], CONFIGS["cfg1"], CONFIGS["cfg4"]
     return {

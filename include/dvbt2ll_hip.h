@@ -257,6 +257,35 @@ void dvbt2ll_host_free(void *p);
 #define DVBT2LL_IQ_CF32 0
 #define DVBT2LL_IQ_SC16 1
 int dvbt2ll_chain_set_output(dvbt2ll_chain *h, float gain, int format);
+/* Input format of a PLP (plp = -1: every PLP; default DVBT2LL_INPUT_TS, the transport stream described above).
+ * DVBT2LL_INPUT_BBFRAME: the run calls' ts_dev / ts point to BBFRAMEs the caller built (EN 302 755 5.1: any input
+ * type, NPD, ISSY, either in-band type; e.g. the BBFRAME payloads of a T2-MI stream), and the chain starts after
+ * the mode adaptation: it scrambles each BBFRAME with the BB PRBS, appends the BCH parity and continues as for a
+ * TS.  With L = kbch / 8:
+ *   layout   packed, unscrambled BBFRAMEs of L bytes each (80 header bits, then the data field: kbch bits, MSB
+ *            first), back to back; the chain writes or alters no header, padding or in-band field
+ *   ts_base  the absolute byte offset of the buffer's byte 0 in that BBFRAME stream, a multiple of L
+ *   frames   interleaving frame m of the PLP (T2 frame m for the reference's PLP) consumes FEC blocks
+ *            [m F, (m + 1) F), stream bytes [m F L, (m + 1) F L): nothing before them, no state from frame to frame
+ *   bounds   a run whose BBFRAMEs are not all inside [ts_base, ts_base + ts_len) is DVBT2LL_EINVAL, nothing
+ *            launched; no byte outside the buffer is read.  Stream batches use ts_stride as for a TS; the host
+ *            paths copy exactly the frames' BBFRAMEs
+ * tsrate is unused; inputmode and inband only set the L1-post fields they set for a TS (the caller declares
+ * there what its BBFRAMEs carry).  sync_errors counts nothing for such a PLP.  get_info / get_plp_info report
+ * ts_bytes_per_frame = F L and payload_bytes_per_block = L while the PLP is in this format.
+ * Applies to later run calls, of every form (device, streams, plps, groups, host, the streaming ring), and on
+ * ordinary, multi-PLP (the format is per PLP) and MISO pair handles; synchronises the device, and in graph mode
+ * drops the instantiated graphs.  An unknown format or PLP index is DVBT2LL_EINVAL.  get_input returns the
+ * PLP's format or DVBT2LL_EINVAL. */
+#define DVBT2LL_INPUT_TS 0
+#define DVBT2LL_INPUT_BBFRAME 1
+int dvbt2ll_chain_set_input(dvbt2ll_chain *h, int plp, int format);
+int dvbt2ll_chain_get_input(const dvbt2ll_chain *h, int plp);
+/* BBFRAME input: the BBFRAMEs consumed by all run calls so far whose header byte 9 is neither the CRC-8 (DVB-S2,
+ * generator 0xD5) of bytes 0 .. 8 nor that value XOR 1 (the HEM mode bit, EN 302 755 5.1.7); each BBFRAME is
+ * counted once per run, and the output does not depend on it.  DFL and MATYPE are not validated.  Synchronises
+ * the device */
+int dvbt2ll_chain_bbheader_errors(dvbt2ll_chain *h, int64_t *count);
 /* per-stage kernel timing with HIP events on the launch stream: enable, then read the
  * accumulated milliseconds and launch counts of stages {0: fec, 1: map, 2: ofdm, 3: reserved (0)};
  * nstages <= 4.  The frames' L1-post signalling is generated on the GPU every run by extra
