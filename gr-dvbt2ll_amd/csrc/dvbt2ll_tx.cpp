@@ -8,9 +8,16 @@
 //   dvbt2ll_tx --preset cfg3 --in stream.ts --out iq.sc16 --format sc16 --gain 0.2
 //   dvbt2ll_tx --mplp mix_4k --in plp0.ts --in plp1.ts --in plp2.ts --out iq.cf32
 //   dvbt2ll_tx --preset cfg3 --input bbframe --in frames.bbf --out iq.cf32
+//   dvbt2ll_tx --mplp mplp3_4k --input t2mi --pid 4096 --in gateway.ts --out iq.cf32
 //
 // --input bbframe reads a file of packed, unscrambled BBFRAMEs (kbch / 8 bytes each, back to back: what a T2
-// gateway built, e.g. the BBFRAME payloads of a T2-MI stream) in place of a TS (dvbt2ll_chain_set_input).
+// gateway built) in place of a TS (dvbt2ll_chain_set_input).
+//
+// --input t2mi reads a transport stream carrying T2-MI (ETSI TS 102 773, DVB data piping) on --pid: the file is
+// de-encapsulated on the GPU in chunks (dvbt2ll_t2mi_run_host, continued from each call's resume position), every
+// PLP's BBFRAMEs are collected, and whole frames are encoded as they complete.  It works with single-PLP presets
+// and with --mplp presets (one --in file for all PLPs; --plp-id per PLP, default 0, 1, ...).  Every interleaving
+// frame must carry the preset's number of FEC blocks: dynamic PLP_NUM_BLOCKS is not supported and is refused.
 //
 // --mplp runs a multi-PLP frame preset (one TS file per PLP, dvbt2ll_chain_create_mplp / _run_plps_host;
 // batches are whole launch units, dvbt2ll_chain_unit_frames).
@@ -81,8 +88,12 @@ void usage(FILE *f) {
                "                          inputmode reservedbiasbits l1scrambled inband; pilotgen:\n"
                "                          misogroup equalization bandwidth; bbheaderbch: tsrate)\n"
                "                          misogroup: 0 TX1, 1 TX2 (pilots only), 2 TX2 with MISO processing\n"
-               "  --input ts|bbframe      what --in holds: an MPEG-TS (default), or packed unscrambled BBFRAMEs\n"
-               "                          of kbch / 8 bytes each (single-PLP presets)\n"
+               "  --input ts|bbframe|t2mi what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
+               "                          of kbch / 8 bytes each (single-PLP presets), or a TS carrying T2-MI\n"
+               "                          (one file; single-PLP and --mplp presets)\n"
+               "  --pid N                 --input t2mi: the PID of the T2-MI stream (default 4096)\n"
+               "  --plp-id K              --input t2mi: the PLP_ID feeding the next PLP of the preset (repeat per\n"
+               "                          PLP; default 0, 1, ...)\n"
                "  --format cf32|sc16      IQ sample format (default cf32, pilotgen's complex64)\n"
                "  --gain G                output gain (the flowgraph's multiply_const; default 1)\n"
                "  --frames N              T2 frames to encode (default: as many as the input holds)\n"
@@ -137,9 +148,153 @@ struct TsIn {
   }
 };
 
+constexpr int kInputT2mi = 2;   // --input t2mi (the chain itself runs in DVBT2LL_INPUT_BBFRAME)
+
+// --input t2mi: the file's TS -> T2-MI deframer in chunks -> per-PLP BBFRAME queues -> whole launch units through
+// dvbt2ll_chain_run_plps_host.  h: a chain of any preset, already in BBFRAME input with its output set.
+int run_t2mi(dvbt2ll_chain *h, const std::string &in_path, const std::string &out_path, int fmt, int pid,
+             const std::vector<int> &plp_ids, int64_t frames, int batch, int device) {
+  const int nplp = dvbt2ll_chain_num_plps(h), unit = dvbt2ll_chain_unit_frames(h);
+  if (!plp_ids.empty() && (int)plp_ids.size() != nplp) {
+    std::fprintf(stderr, "dvbt2ll_tx: --plp-id: give one per PLP (%d)\n", nplp);
+    return 2;
+  }
+  if (batch % unit) { std::fprintf(stderr, "dvbt2ll_tx: --batch must be a multiple of the launch unit %d\n", unit); return 2; }
+  dvbt2ll_chain_info pi[DVBT2LL_MAX_PLP];
+  int st = 0;
+  for (int k = 0; k < nplp && !st; k++) st = dvbt2ll_chain_get_plp_info(h, k, &pi[k]);
+  dvbt2ll_t2mi_params tp;
+  std::memset(&tp, 0, sizeof(tp));
+  tp.pid = pid;
+  tp.stream_id = -1;
+  const int64_t chunk = 188 * 22310;   // about 4 MiB of TS per deframer call
+  tp.max_ts_bytes = chunk;
+  tp.max_packets = 65536;
+  dvbt2ll_t2mi *de = nullptr;
+  if (!st) st = dvbt2ll_t2mi_params_from_chain(h, plp_ids.empty() ? nullptr : plp_ids.data(), &tp);
+  if (!st) st = dvbt2ll_t2mi_create(&tp, device, &de);
+  if (st) { std::fprintf(stderr, "dvbt2ll_tx: t2mi: %s\n", dvbt2ll_strerror(st)); return 1; }
+  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
+  FILE *fout = out_path == "-" ? stdout : std::fopen(out_path.c_str(), "wb");
+  if (!fin || !fout) {
+    std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : out_path.c_str(), std::strerror(errno));
+    dvbt2ll_t2mi_destroy(de);
+    return 1;
+  }
+  const size_t sb = fmt == DVBT2LL_IQ_SC16 ? 4 : 8;
+  std::vector<uint8_t> win, iq((size_t)batch * pi[0].iq_samples_per_frame * sb);
+  std::vector<uint8_t> tmp[DVBT2LL_MAX_PLP], q[DVBT2LL_MAX_PLP];   // a call's blocks; the queue of validated blocks
+  int64_t q_base[DVBT2LL_MAX_PLP] = {}, cap[DVBT2LL_MAX_PLP] = {}, whole[DVBT2LL_MAX_PLP] = {};
+  int64_t in_frame[DVBT2LL_MAX_PLP] = {}, leading[DVBT2LL_MAX_PLP] = {};
+  bool started[DVBT2LL_MAX_PLP] = {};
+  void *optr[DVBT2LL_MAX_PLP] = {};
+  for (int k = 0; k < nplp; k++) {
+    cap[k] = chunk / tp.bbframe_bytes[k] + 1;
+    tmp[k].resize((size_t)cap[k] * tp.bbframe_bytes[k]);
+    optr[k] = tmp[k].data();
+  }
+  std::vector<dvbt2ll_t2mi_packet> recs;
+  dvbt2ll_t2mi_result tot;
+  std::memset(&tot, 0, sizeof(tot));
+  dvbt2ll_t2mi_pos pos = {0, 0};
+  bool eof = false, refused = false;
+  int64_t done = 0;
+  while (!st && !refused && (frames < 0 || done < frames)) {
+    while (!eof && (int64_t)win.size() < chunk) {
+      const size_t old = win.size();
+      win.resize((size_t)chunk);
+      const size_t got = std::fread(win.data() + old, 1, win.size() - old, fin);
+      win.resize(old + got);
+      if (got == 0) eof = true;
+    }
+    const int64_t len = (int64_t)win.size() / 188 * 188;
+    dvbt2ll_t2mi_result res;
+    if ((st = dvbt2ll_t2mi_run_host(de, win.data(), len, &pos, optr, cap, &res))) break;
+    recs.resize((size_t)res.packets);
+    if (res.packets && dvbt2ll_t2mi_get_packets(de, recs.data(), res.packets) != res.packets) { st = DVBT2LL_EDEVICE; break; }
+    int64_t *a = &tot.ts_contributing, *b = &res.ts_contributing;
+    for (int i = 0; i < 15; i++) a[i] += b[i];   // ts_contributing .. accepted
+    tot.packets += res.packets;
+    for (int i = 0; i < 256; i++) tot.by_type[i] += res.by_type[i];
+    // the blocks in stream order: interleaving frames must hold exactly F blocks
+    for (const dvbt2ll_t2mi_packet &r : recs) {
+      if (r.out_index < 0 || r.block < 0) continue;
+      const int k = r.out_index, F = pi[k].fec_blocks_per_frame, L = tp.bbframe_bytes[k];
+      if (r.intl_frame_start) {
+        if (started[k] && in_frame[k] != 0) {
+          std::fprintf(stderr, "dvbt2ll_tx: PLP_ID %d: an interleaving frame of %lld FEC blocks, the preset has %d: "
+                       "dynamic PLP_NUM_BLOCKS is not supported\n", tp.plp_id[k], (long long)in_frame[k], F);
+          refused = true;
+          break;
+        }
+        started[k] = true;
+      } else if (!started[k]) {
+        leading[k]++;   // the tail of an interleaving frame that began before the file
+        continue;
+      } else if (in_frame[k] == 0) {
+        std::fprintf(stderr, "dvbt2ll_tx: PLP_ID %d: an interleaving frame of more than %d FEC blocks: dynamic "
+                     "PLP_NUM_BLOCKS is not supported\n", tp.plp_id[k], F);
+        refused = true;
+        break;
+      }
+      tot.blocks[k]++;
+      q[k].insert(q[k].end(), tmp[k].begin() + (size_t)r.block * L, tmp[k].begin() + (size_t)(r.block + 1) * L);
+      if (++in_frame[k] == F) { in_frame[k] = 0; whole[k]++; }
+    }
+    if (refused) break;
+    // encode the launch units every PLP has whole interleaving frames for
+    for (;;) {
+      int64_t n = frames >= 0 ? std::min<int64_t>(batch, frames - done) : batch;
+      for (int k = 0; k < nplp; k++) n = std::min<int64_t>(n, whole[k] * pi[k].frames_per_if - done);
+      n = n / unit * unit;
+      if (n <= 0) break;
+      const void *ptr[DVBT2LL_MAX_PLP];
+      int64_t base[DVBT2LL_MAX_PLP], ql[DVBT2LL_MAX_PLP];
+      for (int k = 0; k < nplp; k++) { ptr[k] = q[k].data(); base[k] = q_base[k]; ql[k] = (int64_t)q[k].size(); }
+      if ((st = dvbt2ll_chain_run_plps_host(h, ptr, base, ql, done, (int)n, iq.data()))) break;
+      const size_t bytes = (size_t)n * pi[0].iq_samples_per_frame * sb;
+      if (std::fwrite(iq.data(), 1, bytes, fout) != bytes) { st = -1; break; }
+      done += n;
+      for (int k = 0; k < nplp; k++) {   // drop the interleaving frames no later T2 frame needs
+        const int64_t nb = done / pi[k].frames_per_if * pi[k].ts_bytes_per_frame;
+        q[k].erase(q[k].begin(), q[k].begin() + (size_t)(nb - q_base[k]));
+        q_base[k] = nb;
+      }
+    }
+    // continue from the resume position: drop the TS before it
+    const bool progress = res.resume.ts_offset > 0 || res.packets > 0;
+    win.erase(win.begin(), win.begin() + (size_t)res.resume.ts_offset);
+    pos.ts_offset = 0;
+    pos.skip = res.resume.skip;
+    if (eof && (!progress || win.size() < 188)) break;
+    if (!progress && (int64_t)win.size() >= chunk) {
+      std::fprintf(stderr, "dvbt2ll_tx: a T2-MI packet does not complete within %lld bytes of TS\n", (long long)chunk);
+      st = -1;
+    }
+  }
+  if (st) std::fprintf(stderr, "dvbt2ll_tx: t2mi run failed: %s\n", dvbt2ll_strerror(st));
+  std::fprintf(stderr, "dvbt2ll_tx: t2mi: %lld T2 frames; %lld T2-MI packets, accepted %lld, broken %lld, crc_errors %lld, "
+               "filtered %lld, len_errors %lld, other_plp %lld; TS packets: contributing %lld, foreign %lld, null %lld, "
+               "tei %lld, scrambled %lld, bad_sync %lld, no_payload %lld, discontinuities %lld, bad_pointers %lld; blocks",
+               (long long)done, (long long)tot.packets, (long long)tot.accepted, (long long)tot.broken,
+               (long long)tot.crc_errors, (long long)tot.filtered, (long long)tot.len_errors, (long long)tot.other_plp,
+               (long long)tot.ts_contributing, (long long)tot.ts_foreign, (long long)tot.ts_null, (long long)tot.ts_tei,
+               (long long)tot.ts_scrambled, (long long)tot.ts_bad_sync, (long long)tot.ts_no_payload,
+               (long long)tot.discontinuities, (long long)tot.bad_pointers);
+  for (int k = 0; k < nplp; k++)
+    std::fprintf(stderr, " %d:%lld(+%lld before the first frame start)", tp.plp_id[k], (long long)tot.blocks[k],
+                 (long long)leading[k]);
+  std::fprintf(stderr, "\n");
+  if (fin != stdin) std::fclose(fin);
+  if (fout != stdout) std::fclose(fout);
+  dvbt2ll_t2mi_destroy(de);
+  return refused ? 3 : st ? 1 : 0;
+}
+
 // the multi-PLP transmitter: whole launch units per batch, each PLP's TS span from its own file
 int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const std::string &out_path, int fmt,
-             float gain, int64_t frames, int batch, int device, bool print_params) {
+             float gain, int64_t frames, int batch, int device, bool print_params, int input = DVBT2LL_INPUT_TS,
+             int pid = 0, const std::vector<int> &plp_ids = {}) {
   dvbt2ll_mplp_chain_params p;
   std::memset(&p, 0, sizeof(p));
   dvbt2ll_mplp_params &m = p.fm;
@@ -163,8 +318,9 @@ int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const st
     std::printf(" %d\n", m.num_subslices);
     return 0;
   }
-  if ((int)ins.size() != ps.nplp || out_path.empty()) {
-    std::fprintf(stderr, "dvbt2ll_tx: --mplp %s needs %d --in files and --out\n", ps.name, ps.nplp);
+  const bool t2mi = input == kInputT2mi;
+  if ((int)ins.size() != (t2mi ? 1 : ps.nplp) || out_path.empty()) {
+    std::fprintf(stderr, "dvbt2ll_tx: --mplp %s needs %d --in file(s) and --out\n", ps.name, t2mi ? 1 : ps.nplp);
     return 2;
   }
   dvbt2ll_chain *h = nullptr;
@@ -173,10 +329,16 @@ int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const st
   const int unit = st ? 1 : dvbt2ll_chain_unit_frames(h);
   if (!st && batch % unit) st = DVBT2LL_EINVAL;   // batches of whole launch units
   if (!st) st = dvbt2ll_chain_set_output(h, gain, fmt);
+  if (!st && t2mi) st = dvbt2ll_chain_set_input(h, -1, DVBT2LL_INPUT_BBFRAME);
   if (st) {
     std::fprintf(stderr, "dvbt2ll_tx: chain: %s (batch must be a multiple of the launch unit)\n", dvbt2ll_strerror(st));
     dvbt2ll_chain_destroy(h);
     return 1;
+  }
+  if (t2mi) {
+    const int rc = run_t2mi(h, ins[0], out_path, fmt, pid, plp_ids, frames, batch, device);
+    dvbt2ll_chain_destroy(h);
+    return rc;
   }
   dvbt2ll_chain_info pi[DVBT2LL_MAX_PLP];
   std::vector<TsIn> ts(ps.nplp);
@@ -232,7 +394,8 @@ int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const st
 int main(int argc, char **argv) {
   std::string in_path, out_path, preset = "cfg1", mplp;
   std::vector<std::string> sets, ins;
-  int fmt = DVBT2LL_IQ_CF32, input = DVBT2LL_INPUT_TS, batch = 16, device = 0;
+  int fmt = DVBT2LL_IQ_CF32, input = DVBT2LL_INPUT_TS, batch = 16, device = 0, pid = 4096;
+  std::vector<int> plp_ids;
   bool print_params = false;
   int64_t frames = -1;
   float gain = 1.f;
@@ -260,8 +423,11 @@ int main(int argc, char **argv) {
       std::string v = next();
       if (v == "ts") input = DVBT2LL_INPUT_TS;
       else if (v == "bbframe") input = DVBT2LL_INPUT_BBFRAME;
+      else if (v == "t2mi") input = kInputT2mi;
       else { std::fprintf(stderr, "dvbt2ll_tx: unknown input %s\n", v.c_str()); return 2; }
-    } else if (a == "--gain") gain = std::strtof(next(), nullptr);
+    } else if (a == "--pid") pid = (int)std::strtol(next(), nullptr, 0);
+    else if (a == "--plp-id") plp_ids.push_back((int)std::strtol(next(), nullptr, 0));
+    else if (a == "--gain") gain = std::strtof(next(), nullptr);
     else if (a == "--frames") frames = std::strtoll(next(), nullptr, 10);
     else if (a == "--batch") batch = std::atoi(next());
     else if (a == "--device") device = std::atoi(next());
@@ -270,9 +436,10 @@ int main(int argc, char **argv) {
   }
 
   if (!mplp.empty()) {
-    if (input != DVBT2LL_INPUT_TS) { std::fprintf(stderr, "dvbt2ll_tx: --input bbframe takes a single-PLP preset\n"); return 2; }
+    if (input == DVBT2LL_INPUT_BBFRAME) { std::fprintf(stderr, "dvbt2ll_tx: --input bbframe takes a single-PLP preset\n"); return 2; }
     for (auto &q : kMplpPresets)
-      if (mplp == q.name) return run_mplp(q, ins, out_path, fmt, gain, frames, batch, device, print_params);
+      if (mplp == q.name)
+        return run_mplp(q, ins, out_path, fmt, gain, frames, batch, device, print_params, input, pid, plp_ids);
     std::fprintf(stderr, "dvbt2ll_tx: unknown multi-PLP preset %s\n", mplp.c_str());
     return 2;
   }
@@ -307,11 +474,17 @@ int main(int argc, char **argv) {
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: chain create: %s\n", dvbt2ll_strerror(st)); return 1; }
   dvbt2ll_chain_info info;
   // (the info after set_input: it then counts whole BBFRAMEs)
-  if ((st = dvbt2ll_chain_set_input(h, -1, input)) || (st = dvbt2ll_chain_get_info(h, &info)) ||
+  const bool t2mi = input == kInputT2mi;
+  if ((st = dvbt2ll_chain_set_input(h, -1, t2mi ? DVBT2LL_INPUT_BBFRAME : input)) || (st = dvbt2ll_chain_get_info(h, &info)) ||
       (st = dvbt2ll_chain_set_output(h, gain, fmt))) {
     std::fprintf(stderr, "dvbt2ll_tx: %s\n", dvbt2ll_strerror(st));
     dvbt2ll_chain_destroy(h);
     return 1;
+  }
+  if (t2mi) {
+    const int rc = run_t2mi(h, in_path, out_path, fmt, pid, plp_ids, frames, batch, device);
+    dvbt2ll_chain_destroy(h);
+    return rc;
   }
   FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
   FILE *fout = out_path == "-" ? stdout : std::fopen(out_path.c_str(), "wb");

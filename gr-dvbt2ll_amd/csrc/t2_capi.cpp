@@ -17,6 +17,7 @@
 #include "../../include/dvbt2ll_hip.h"
 #include "t2_kernels.h"
 #include "t2_plan.h"
+#include "t2mi_kernels.h"
 
 using namespace t2;
 
@@ -1853,3 +1854,167 @@ extern "C" int dvbt2ll_chain_synchronize(dvbt2ll_chain *h) {
   return DVBT2LL_OK;
 }
 extern "C" void dvbt2ll_chain_destroy(dvbt2ll_chain *h) { delete h; }
+
+// ============================================================================ T2-MI input
+// A handle beside the chain: its scratch (sized at create from max_ts_bytes and max_packets), no stream state.  All
+// passes of a run go to the caller's stream (t2mi_kernels.hip); the result stays on the device until get_result.
+struct dvbt2ll_t2mi {
+  DeviceCtx ctx;
+  dvbt2ll_t2mi_params p{};
+  T2miDev dev;
+  DevBuf scratch, ts_tmp, out_tmp[DVBT2LL_MAX_PLP];
+  hipEvent_t done = nullptr;     // the last run; a run on another stream waits for it (the scratch is shared)
+  hipStream_t last = nullptr;
+  bool ran = false;
+  ~dvbt2ll_t2mi() {
+    if (done) { (void)hipSetDevice(ctx.device); (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+  }
+};
+
+static bool t2mi_valid_len(int L) {
+  static const int kbch[14] = {32208, 38688, 43040, 48408, 51648, 53840, 7032, 9552, 10632, 11712, 12432, 13152,
+                               5232, 6312};   // the codes of build_fec (t2_plan.cpp fec_numbers)
+  for (int k : kbch)
+    if (L == k / 8) return true;
+  return false;
+}
+
+static bool t2mi_params_ok(const dvbt2ll_t2mi_params &p) {
+  if (p.pid < 0 || p.pid > 0x1FFE || p.stream_id < -1 || p.stream_id > 7) return false;
+  if (p.nplp < 1 || p.nplp > DVBT2LL_MAX_PLP) return false;
+  if (p.max_ts_bytes < 188 || p.max_ts_bytes % 188 || p.max_ts_bytes >= ((int64_t)1 << 31)) return false;
+  if (p.max_packets < 1 || p.max_packets > (1 << 28)) return false;
+  for (int k = 0; k < p.nplp; k++) {
+    if (p.plp_id[k] < 0 || p.plp_id[k] > 255 || !t2mi_valid_len(p.bbframe_bytes[k])) return false;
+    for (int j = 0; j < k; j++)
+      if (p.plp_id[j] == p.plp_id[k]) return false;
+  }
+  return true;
+}
+
+extern "C" int dvbt2ll_t2mi_create(const dvbt2ll_t2mi_params *p, int device, dvbt2ll_t2mi **out) {
+  if (!p || !out) return DVBT2LL_EINVAL;
+  *out = nullptr;
+  if (!t2mi_params_ok(*p)) return DVBT2LL_EINVAL;
+  std::unique_ptr<dvbt2ll_t2mi> h(new (std::nothrow) dvbt2ll_t2mi());
+  if (!h) return DVBT2LL_ENOMEM;
+  h->p = *p;
+  int r = h->ctx.init(device);
+  if (r) return r;
+  T2miDev &d = h->dev;
+  d.pid = p->pid;
+  d.stream_id = p->stream_id;
+  d.nplp = p->nplp;
+  for (int k = 0; k < p->nplp; k++) { d.plp_id[k] = p->plp_id[k]; d.L[k] = p->bbframe_bytes[k]; }
+  d.max_ts = (uint32_t)(p->max_ts_bytes / 188);
+  d.max_packets = (uint32_t)p->max_packets;
+  if (h->scratch.ensure(t2mi_layout(d, nullptr))) return DVBT2LL_ENOMEM;
+  (void)t2mi_layout(d, h->scratch.p);
+  std::vector<uint32_t> tab(T2MI_TAB_WORDS);
+  t2mi_host_tables(tab.data());
+  HIP_TRY(hipMemcpy(d.tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d.res, 0, T2MI_R_WORDS * 8));
+  HIP_TRY(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+  *out = h.release();
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_t2mi_params_from_chain(const dvbt2ll_chain *chain, const int *plp_ids, dvbt2ll_t2mi_params *p) {
+  if (!chain || !p || chain->nplp < 1 || chain->nplp > DVBT2LL_MAX_PLP) return DVBT2LL_EINVAL;
+  p->nplp = chain->nplp;
+  for (int k = 0; k < chain->nplp; k++) {
+    p->plp_id[k] = plp_ids ? plp_ids[k] : k;
+    p->bbframe_bytes[k] = (int)chain->plps[k]->bbf_len();
+  }
+  return DVBT2LL_OK;
+}
+
+static int t2mi_run_args(const dvbt2ll_t2mi *h, const void *ts, int64_t ts_len, const dvbt2ll_t2mi_pos *start,
+                         void *const *out, const int64_t *cap, T2miRun &r) {
+  if (!h || !ts || !start || !out || !cap) return DVBT2LL_EINVAL;
+  if (ts_len < 0 || ts_len % 188 || ts_len > h->p.max_ts_bytes) return DVBT2LL_EINVAL;
+  if (start->ts_offset < 0 || start->ts_offset % 188 || start->ts_offset > ts_len || start->skip < 0)
+    return DVBT2LL_EINVAL;
+  for (int k = 0; k < h->p.nplp; k++)
+    if (!out[k] || cap[k] < 0) return DVBT2LL_EINVAL;
+  r.ts = (const uint8_t *)ts;
+  r.i0 = (uint32_t)(start->ts_offset / 188);
+  r.n = (uint32_t)(ts_len / 188) - r.i0;
+  r.skip = (uint32_t)start->skip;
+  for (int k = 0; k < h->p.nplp; k++) {
+    r.out[k] = (uint8_t *)out[k];
+    r.cap[k] = (uint32_t)std::min<int64_t>(cap[k], (int64_t)1 << 30);
+  }
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_t2mi_run_device(dvbt2ll_t2mi *h, const void *ts_dev, int64_t ts_len,
+                                       const dvbt2ll_t2mi_pos *start, void *const *out_dev,
+                                       const int64_t *out_cap_blocks, void *stream) {
+  T2miRun r;
+  int e = t2mi_run_args(h, ts_dev, ts_len, start, out_dev, out_cap_blocks, r);
+  if (e) return e;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->ctx.stream;
+  if (h->ran && h->last != st) HIP_TRY(hipStreamWaitEvent(st, h->done, 0));
+  HIP_TRY(t2mi_launch(h->dev, r, st));
+  HIP_TRY(hipEventRecord(h->done, st));
+  h->last = st;
+  h->ran = true;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_t2mi_get_result(dvbt2ll_t2mi *h, dvbt2ll_t2mi_result *res) {
+  if (!h || !res) return DVBT2LL_EINVAL;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  std::vector<uint64_t> w(T2MI_R_WORDS);
+  HIP_TRY(hipMemcpy(w.data(), h->dev.res, w.size() * 8, hipMemcpyDeviceToHost));
+  memset(res, 0, sizeof *res);
+  res->resume.ts_offset = (int64_t)w[T2MI_R_OFFSET];
+  res->resume.skip = (int)w[T2MI_R_SKIP];
+  res->packets = (int64_t)w[T2MI_R_PACKETS];
+  int64_t *ts = &res->ts_contributing, *pk = &res->broken;
+  for (int k = 0; k < 9; k++) ts[k] = (int64_t)w[T2MI_R_TS + k];
+  for (int k = 0; k < 6; k++) pk[k] = (int64_t)w[T2MI_R_PKT + k];
+  for (int k = 0; k < DVBT2LL_MAX_PLP; k++) res->blocks[k] = (int64_t)w[T2MI_R_BLOCKS + k];
+  for (int k = 0; k < 256; k++) res->by_type[k] = (int64_t)w[T2MI_R_TYPE + k];
+  return DVBT2LL_OK;
+}
+
+extern "C" int64_t dvbt2ll_t2mi_get_packets(dvbt2ll_t2mi *h, dvbt2ll_t2mi_packet *out, int64_t max_records) {
+  static_assert(sizeof(dvbt2ll_t2mi_packet) == sizeof(T2miRec), "table record layout");
+  if (!h || !out || max_records < 0) return DVBT2LL_EINVAL;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  uint64_t n = 0;
+  HIP_TRY(hipMemcpy(&n, h->dev.res + T2MI_R_PACKETS, 8, hipMemcpyDeviceToHost));
+  const int64_t m = std::min<int64_t>((int64_t)n, max_records);
+  if (m > 0) HIP_TRY(hipMemcpy(out, h->dev.table, (size_t)m * sizeof(T2miRec), hipMemcpyDeviceToHost));
+  return m;
+}
+
+extern "C" int dvbt2ll_t2mi_run_host(dvbt2ll_t2mi *h, const void *ts, int64_t ts_len, const dvbt2ll_t2mi_pos *start,
+                                     void *const *out, const int64_t *out_cap_blocks, dvbt2ll_t2mi_result *res) {
+  T2miRun r;
+  if (!res) return DVBT2LL_EINVAL;
+  int e = t2mi_run_args(h, ts, ts_len, start, out, out_cap_blocks, r);
+  if (e) return e;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  if (h->ts_tmp.ensure((size_t)std::max<int64_t>(ts_len, 1))) return DVBT2LL_ENOMEM;
+  void *od[DVBT2LL_MAX_PLP] = {};
+  for (int k = 0; k < h->p.nplp; k++) {
+    if (h->out_tmp[k].ensure((size_t)r.cap[k] * h->p.bbframe_bytes[k] + 16)) return DVBT2LL_ENOMEM;
+    od[k] = h->out_tmp[k].p;
+  }
+  if (ts_len) HIP_TRY(hipMemcpyAsync(h->ts_tmp.p, ts, (size_t)ts_len, hipMemcpyHostToDevice, h->ctx.stream));
+  if ((e = dvbt2ll_t2mi_run_device(h, h->ts_tmp.p, ts_len, start, od, out_cap_blocks, h->ctx.stream))) return e;
+  if ((e = dvbt2ll_t2mi_get_result(h, res))) return e;
+  for (int k = 0; k < h->p.nplp; k++)
+    if (res->blocks[k] > 0)
+      HIP_TRY(hipMemcpy(out[k], od[k], (size_t)res->blocks[k] * h->p.bbframe_bytes[k], hipMemcpyDeviceToHost));
+  return DVBT2LL_OK;
+}
+
+extern "C" void dvbt2ll_t2mi_destroy(dvbt2ll_t2mi *h) { delete h; }

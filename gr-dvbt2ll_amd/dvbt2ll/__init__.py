@@ -9,6 +9,7 @@ from .enums import *  # noqa: F401,F403
 from .blocks import bbheaderbch_bb, ldpc_bb, interleavermod_bc, framemapperfint_cc, pilotgenp1insert_cc  # noqa: F401
 from .blocks import framemapper_mplp_cc  # noqa: F401
 from .chain import Chain, IQ_CF32, IQ_SC16, INPUT_TS, INPUT_BBFRAME  # noqa: F401
+from .t2mi import T2miDeframer, T2miResult  # noqa: F401
 from .configs import CONFIGS, T2Config, ts_packets, ts_for_frames, bbframe_span  # noqa: F401
 from .configs import MPLP_CONFIGS, MplpConfig, PlpConfig  # noqa: F401
 from .configs import MISO_TX2_PROCESSED  # noqa: F401

@@ -88,6 +88,23 @@ class _ChainInfo(ctypes.Structure):
                 ("cw_stride_bytes", ctypes.c_int64), ("frames_per_if", ctypes.c_int)]
 
 
+class _T2miParams(ctypes.Structure):
+    _fields_ = [("pid", ctypes.c_int), ("stream_id", ctypes.c_int), ("nplp", ctypes.c_int),
+                ("plp_id", ctypes.c_int * MAX_PLP), ("bbframe_bytes", ctypes.c_int * MAX_PLP),
+                ("max_ts_bytes", ctypes.c_int64), ("max_packets", ctypes.c_int)]
+
+
+class _T2miPos(ctypes.Structure):
+    _fields_ = [("ts_offset", ctypes.c_int64), ("skip", ctypes.c_int)]
+
+
+class _T2miResult(ctypes.Structure):
+    _fields_ = [("resume", _T2miPos), ("packets", ctypes.c_int64)] + [(n, ctypes.c_int64) for n in (
+        "ts_contributing", "ts_foreign", "ts_null", "ts_tei", "ts_scrambled", "ts_bad_sync", "ts_no_payload",
+        "discontinuities", "bad_pointers", "broken", "crc_errors", "filtered", "len_errors", "other_plp",
+        "accepted")] + [("blocks", ctypes.c_int64 * MAX_PLP), ("by_type", ctypes.c_int64 * 256)]
+
+
 BLOCKS = ("bbheaderbch", "ldpc", "interleavermod", "framemapperfint", "pilotgenp1insert")
 PARAMS = {"bbheaderbch": _BbParams, "ldpc": _LdpcParams, "interleavermod": _ImParams,
           "framemapperfint": _FmParams, "pilotgenp1insert": _PgParams}
@@ -109,6 +126,8 @@ EXPORTS += ["dvbt2ll_chain_" + f for f in ("create_mplp", "num_plps", "unit_fram
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create_miso_pair", "create_mplp_miso_pair", "num_groups", "run_groups",
                                            "run_plps_groups")]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("set_input", "get_input", "bbheader_errors")]
+EXPORTS += ["dvbt2ll_t2mi_" + f for f in ("create", "params_from_chain", "run_device", "get_result", "get_packets",
+                                          "run_host", "destroy")]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create", "get_info", "run_device", "run_streams", "run_host", "set_output", "set_slots", "set_graph", "set_timing",
                                            "get_timing", "debug_codewords", "debug_cell_pairs", "debug_cells",
                                            "synchronize", "sync_errors",
@@ -196,6 +215,17 @@ def lib():
     L.dvbt2ll_chain_set_input.argtypes = [vp, ci, ci]
     L.dvbt2ll_chain_get_input.argtypes = [vp, ci]
     L.dvbt2ll_chain_bbheader_errors.argtypes = [vp, ctypes.POINTER(i64)]
+    L.dvbt2ll_t2mi_create.argtypes = [ctypes.POINTER(_T2miParams), ci, ctypes.POINTER(vp)]
+    L.dvbt2ll_t2mi_params_from_chain.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(_T2miParams)]
+    L.dvbt2ll_t2mi_run_device.argtypes = [vp, vp, i64, ctypes.POINTER(_T2miPos), ctypes.POINTER(vp),
+                                          ctypes.POINTER(i64), vp]
+    L.dvbt2ll_t2mi_get_result.argtypes = [vp, ctypes.POINTER(_T2miResult)]
+    L.dvbt2ll_t2mi_get_packets.argtypes = [vp, vp, i64]
+    L.dvbt2ll_t2mi_get_packets.restype = i64
+    L.dvbt2ll_t2mi_run_host.argtypes = [vp, vp, i64, ctypes.POINTER(_T2miPos), ctypes.POINTER(vp),
+                                        ctypes.POINTER(i64), ctypes.POINTER(_T2miResult)]
+    L.dvbt2ll_t2mi_destroy.argtypes = [vp]
+    L.dvbt2ll_t2mi_destroy.restype = None
     L.dvbt2ll_chain_destroy.argtypes = [vp]
     L.dvbt2ll_chain_destroy.restype = None
     _lib = L

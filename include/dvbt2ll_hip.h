@@ -259,9 +259,9 @@ void dvbt2ll_host_free(void *p);
 int dvbt2ll_chain_set_output(dvbt2ll_chain *h, float gain, int format);
 /* Input format of a PLP (plp = -1: every PLP; default DVBT2LL_INPUT_TS, the transport stream described above).
  * DVBT2LL_INPUT_BBFRAME: the run calls' ts_dev / ts point to BBFRAMEs the caller built (EN 302 755 5.1: any input
- * type, NPD, ISSY, either in-band type; e.g. the BBFRAME payloads of a T2-MI stream), and the chain starts after
- * the mode adaptation: it scrambles each BBFRAME with the BB PRBS, appends the BCH parity and continues as for a
- * TS.  With L = kbch / 8:
+ * type, NPD, ISSY, either in-band type; e.g. what dvbt2ll_t2mi_run_device wrote from a T2-MI stream), and the chain
+ * starts after the mode adaptation: it scrambles each BBFRAME with the BB PRBS, appends the BCH parity and continues
+ * as for a TS.  With L = kbch / 8:
  *   layout   packed, unscrambled BBFRAMEs of L bytes each (80 header bits, then the data field: kbch bits, MSB
  *            first), back to back; the chain writes or alters no header, padding or in-band field
  *   ts_base  the absolute byte offset of the buffer's byte 0 in that BBFRAME stream, a multiple of L
@@ -430,6 +430,97 @@ int dvbt2ll_chain_run_groups(dvbt2ll_chain *h, const void *ts_dev, int64_t ts_st
 int dvbt2ll_chain_run_plps_groups(dvbt2ll_chain *h, const void *const *ts_dev, const int64_t *ts_base,
                                   const int64_t *ts_len, int64_t first_frame, int nframes, void *const iq_dev[2],
                                   void *stream);
+
+/* ---------------------------------------------------------------------------
+ * T2-MI input (ETSI TS 102 773 over DVB data piping): a device buffer of 188-byte TS packets -> per-PLP packed
+ * BBFRAME streams in the layout DVBT2LL_INPUT_BBFRAME reads (L = kbch / 8 bytes per block, back to back), a packet
+ * table and counters.  A handle of its own beside the chain: it holds scratch, no stream state, and composes with
+ * every run form.  The reference has no T2-MI code: PARITY UNPINNED, pinned by tests/t2mi_ref.py's sequential
+ * restatement and known answers.
+ *
+ * TS layer   packets of PID pid with a payload (AFC 01: bytes 4 .. 187; AFC 11: bytes 5 + a .. 187, a = byte 4),
+ *            TEI = 0 and scrambling = 0 contribute; with PUSI the first payload byte is the pointer_field p, which
+ *            is removed.  The remaining payloads, concatenated, are the T2-MI byte stream.  A contributing packet
+ *            whose continuity counter is not its predecessor's + 1 mod 16 is a discontinuity at its first stream
+ *            byte (the first contributing packet of a call has no predecessor).
+ * packets    6 header bytes (packet_type 8, packet_count 8, superframe_idx 4, rfu 9, t2mi_stream_id 3,
+ *            payload_len 16 in bits), ceil(payload_len / 8) payload bytes, CRC-32/MPEG-2 of all of it: T = 10 +
+ *            ceil(payload_len / 8) bytes.  Type 0x00: frame_idx 8, plp_id 8, intl_frame_start 1, rfu 7, BBFRAME.
+ * starts     p bytes into a contributing PUSI packet's stripped payload (p past its end: counted in bad_pointers,
+ *            no start); and, where the packet at a start ends inside the same TS packet's payload, the next byte.
+ * a packet   at start s is complete when s + T <= the stream length; consistent when no other start lies in
+ *            (s, s + T) and no discontinuity in (s, s + T) (one exactly at s is a packet that begins a TS packet
+ *            after a loss: intact, and a call that resumes there could not see it); accepted when complete,
+ *            consistent, the CRC matches and (stream_id < 0 or t2mi_stream_id == stream_id).
+ * output     an accepted type-0 packet of mapped plp_id[o] with payload_len == 24 + 8 bbframe_bytes[o] is block n
+ *            of out_dev[o], n = its rank among such packets of the call; otherwise len_errors / other_plp.
+ * prefix     the call emits (table, outputs, counters) the longest prefix of packets in stream order in which
+ *            every packet is complete, no output's capacity and not max_packets is exceeded.  The resume position
+ *            is the byte offset of the TS packet holding the first packet not emitted and the number of starts in
+ *            that TS packet already emitted; (ts_len, 0) when nothing is left (a call whose start is at ts_len
+ *            returns its start).  The TS-level counters count the TS packets before the resume position, so every
+ *            counter adds up over chained calls -- except a discontinuity at a call's first contributing packet.
+ * bounds     nothing outside [ts_dev, ts_dev + ts_len) is read, nothing outside out_cap_blocks[o] blocks of
+ *            out_dev[o] is written, whatever the stream's length fields say.
+ * ------------------------------------------------------------------------- */
+typedef struct dvbt2ll_t2mi dvbt2ll_t2mi;
+typedef struct {
+  int pid;                               /* 0 .. 0x1FFE */
+  int stream_id;                         /* -1: any; 0 .. 7: accept only this t2mi_stream_id */
+  int nplp;                              /* 1 .. DVBT2LL_MAX_PLP outputs */
+  int plp_id[DVBT2LL_MAX_PLP];           /* 0 .. 255, distinct */
+  int bbframe_bytes[DVBT2LL_MAX_PLP];    /* L = kbch / 8 of one of the standard's 14 codes */
+  int64_t max_ts_bytes;                  /* largest ts_len of a run, a multiple of 188 below 2^31 */
+  int max_packets;                       /* table capacity: T2-MI packets emitted per run */
+} dvbt2ll_t2mi_params;
+typedef struct {
+  int64_t ts_offset;                     /* a multiple of 188 in [0, ts_len] */
+  int skip;                              /* starts of that TS packet already emitted */
+} dvbt2ll_t2mi_pos;
+/* one table record, 24 bytes, little-endian; ts_index / ts_byte are in ts_dev's coordinates */
+#define DVBT2LL_T2MI_COMPLETE 1
+#define DVBT2LL_T2MI_CONSISTENT 2
+#define DVBT2LL_T2MI_CRC_OK 4
+#define DVBT2LL_T2MI_ACCEPTED 8
+typedef struct {
+  uint32_t ts_index;                     /* TS packet holding the T2-MI packet's first byte */
+  uint32_t ts_byte;                      /* byte offset of that first byte in the TS buffer */
+  uint8_t packet_type, packet_count, superframe_idx, t2mi_stream_id;
+  uint16_t payload_len;                  /* bits */
+  uint8_t flags;                         /* DVBT2LL_T2MI_* */
+  uint8_t intl_frame_start;              /* type 0x00 with payload_len >= 24 (else 0, as the next two) */
+  uint8_t frame_idx, plp_id;
+  int8_t out_index;                      /* output written, or -1 */
+  uint8_t reserved;
+  int32_t block;                         /* block rank in that output, or -1 */
+} dvbt2ll_t2mi_packet;
+typedef struct {
+  dvbt2ll_t2mi_pos resume;
+  int64_t packets;                       /* table records of the call */
+  int64_t ts_contributing, ts_foreign, ts_null, ts_tei, ts_scrambled, ts_bad_sync, ts_no_payload, discontinuities,
+      bad_pointers;
+  int64_t broken, crc_errors, filtered, len_errors, other_plp, accepted;
+  int64_t blocks[DVBT2LL_MAX_PLP];       /* blocks written per output */
+  int64_t by_type[256];                  /* table records per packet_type */
+} dvbt2ll_t2mi_result;
+int dvbt2ll_t2mi_create(const dvbt2ll_t2mi_params *p, int device, dvbt2ll_t2mi **out);
+/* fills nplp, plp_id[k] = plp_ids[k] (NULL: k) and bbframe_bytes[k] from the chain's PLP k; the other fields stay */
+int dvbt2ll_t2mi_params_from_chain(const dvbt2ll_chain *chain, const int *plp_ids, dvbt2ll_t2mi_params *p);
+/* ts_dev: ts_len bytes (a multiple of 188, <= max_ts_bytes) on the device; start: (0, 0) or a previous call's resume
+ * position for this buffer; out_dev[o]: room for out_cap_blocks[o] blocks of bbframe_bytes[o].  Asynchronous on
+ * stream (NULL: the handle's own); no host round trip.  One run of a handle at a time: the next run call on another
+ * stream first waits for the previous one.  DVBT2LL_EINVAL, nothing launched: ts_len not a multiple of 188 or above
+ * max_ts_bytes, start outside the buffer or off a packet boundary, skip < 0, a negative capacity, a null pointer. */
+int dvbt2ll_t2mi_run_device(dvbt2ll_t2mi *h, const void *ts_dev, int64_t ts_len, const dvbt2ll_t2mi_pos *start,
+                            void *const *out_dev, const int64_t *out_cap_blocks, void *stream);
+/* synchronises with the last run and returns its result */
+int dvbt2ll_t2mi_get_result(dvbt2ll_t2mi *h, dvbt2ll_t2mi_result *res);
+/* the last run's table: up to max_records records to host memory; returns the number copied, or a negative status */
+int64_t dvbt2ll_t2mi_get_packets(dvbt2ll_t2mi *h, dvbt2ll_t2mi_packet *out, int64_t max_records);
+/* host buffers, synchronous: the TS is copied in, each output's written blocks are copied out */
+int dvbt2ll_t2mi_run_host(dvbt2ll_t2mi *h, const void *ts, int64_t ts_len, const dvbt2ll_t2mi_pos *start,
+                          void *const *out, const int64_t *out_cap_blocks, dvbt2ll_t2mi_result *res);
+void dvbt2ll_t2mi_destroy(dvbt2ll_t2mi *h);
 
 /* ---------------------------------------------------------------------------
  * ABI version.  The parameter and info structs are passed by pointer with no size field, so a caller
