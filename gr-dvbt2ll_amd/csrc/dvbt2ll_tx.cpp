@@ -19,6 +19,11 @@
 // and with --mplp presets (one --in file for all PLPs; --plp-id per PLP, default 0, 1, ...).  Every interleaving
 // frame must carry the preset's number of FEC blocks: dynamic PLP_NUM_BLOCKS is not supported and is refused.
 //
+// --input ts-npd reads an ordinary (multi-programme) TS and builds the BBFRAMEs itself on the GPU, in high-efficiency
+// mode with null-packet deletion (dvbt2ll_modeadapt_run_host in chunks, continued from each call's resume position,
+// flushed at the end of the file): --pids a,b,... selects the PLP's PIDs (default: every PID but 0x1FFF).  With
+// --mplp presets the one --in file feeds every PLP, each through an adapter of its own: repeat --pids per PLP.
+//
 // --mplp runs a multi-PLP frame preset (one TS file per PLP, dvbt2ll_chain_create_mplp / _run_plps_host;
 // batches are whole launch units, dvbt2ll_chain_unit_frames).
 //
@@ -88,9 +93,12 @@ void usage(FILE *f) {
                "                          inputmode reservedbiasbits l1scrambled inband; pilotgen:\n"
                "                          misogroup equalization bandwidth; bbheaderbch: tsrate)\n"
                "                          misogroup: 0 TX1, 1 TX2 (pilots only), 2 TX2 with MISO processing\n"
-               "  --input ts|bbframe|t2mi what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
+               "  --input ts|bbframe|t2mi|ts-npd what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
                "                          of kbch / 8 bytes each (single-PLP presets), or a TS carrying T2-MI\n"
                "                          (one file; single-PLP and --mplp presets)\n"
+               "                          ts-npd: a TS adapted on the GPU to HEM BBFRAMEs with null-packet deletion\n"
+               "  --pids A,B,...          --input ts-npd: the PIDs of the next PLP of the preset (repeat per PLP;\n"
+               "                          default: every PID but 0x1FFF)\n"
                "  --pid N                 --input t2mi: the PID of the T2-MI stream (default 4096)\n"
                "  --plp-id K              --input t2mi: the PLP_ID feeding the next PLP of the preset (repeat per\n"
                "                          PLP; default 0, 1, ...)\n"
@@ -291,10 +299,129 @@ int run_t2mi(dvbt2ll_chain *h, const std::string &in_path, const std::string &ou
   return refused ? 3 : st ? 1 : 0;
 }
 
+constexpr int kInputTsNpd = 3;   // --input ts-npd (the chain itself runs in DVBT2LL_INPUT_BBFRAME)
+
+// --input ts-npd: the file's TS -> one mode adapter per PLP in chunks -> per-PLP BBFRAME queues -> whole launch units
+// through dvbt2ll_chain_run_plps_host.  h: a chain of any preset, already in BBFRAME input with its output set.
+int run_tsnpd(dvbt2ll_chain *h, const std::string &in_path, const std::string &out_path, int fmt,
+              const std::vector<std::vector<int>> &pids, int64_t frames, int batch, int device) {
+  const int nplp = dvbt2ll_chain_num_plps(h), unit = dvbt2ll_chain_unit_frames(h);
+  if (!pids.empty() && (int)pids.size() != nplp) {
+    std::fprintf(stderr, "dvbt2ll_tx: --pids: give one list per PLP (%d)\n", nplp);
+    return 2;
+  }
+  if (batch % unit) { std::fprintf(stderr, "dvbt2ll_tx: --batch must be a multiple of the launch unit %d\n", unit); return 2; }
+  const int64_t chunk = 188 * 22310;   // about 4 MiB of TS per adapter call
+  struct Plp {
+    dvbt2ll_modeadapt *ad = nullptr;
+    FILE *f = nullptr;
+    dvbt2ll_chain_info info;
+    std::vector<uint8_t> win, tmp, q;   // the TS window, one call's BBFRAMEs, the queue
+    dvbt2ll_modeadapt_pos pos = {0, 0, 0};
+    dvbt2ll_modeadapt_result tot;
+    int64_t q_base = 0, L = 0;
+    bool eof = false, done = false;
+  };
+  std::vector<Plp> pl(nplp);
+  int st = 0;
+  for (int k = 0; k < nplp && !st; k++) {
+    Plp &p = pl[k];
+    std::memset(&p.tot, 0, sizeof(p.tot));
+    dvbt2ll_modeadapt_params mp;
+    std::memset(&mp, 0, sizeof(mp));
+    uint8_t mask[1024] = {};
+    if (!pids.empty()) {
+      for (int pid : pids[k])
+        if (pid >= 0 && pid < 0x1FFF) mask[pid >> 3] |= (uint8_t)(1 << (pid & 7));
+      mp.pid_mask = mask;
+    }
+    mp.npd = 1;
+    mp.max_ts_bytes = chunk;
+    if ((st = dvbt2ll_chain_get_plp_info(h, k, &p.info)) || (st = dvbt2ll_modeadapt_params_from_chain(h, k, &mp)) ||
+        (st = dvbt2ll_modeadapt_create(&mp, device, &p.ad)))
+      break;
+    p.L = mp.kbch / 8;
+    p.tmp.resize((size_t)(chunk / (p.L - 10) + 2) * p.L);
+    p.f = std::fopen(in_path.c_str(), "rb");
+    if (!p.f) { std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", in_path.c_str(), std::strerror(errno)); st = -1; }
+  }
+  FILE *fout = st ? nullptr : (out_path == "-" ? stdout : std::fopen(out_path.c_str(), "wb"));
+  if (!st && !fout) { std::fprintf(stderr, "dvbt2ll_tx: cannot open %s\n", out_path.c_str()); st = -1; }
+  const size_t sb = fmt == DVBT2LL_IQ_SC16 ? 4 : 8;
+  std::vector<uint8_t> iq;
+  if (!st) iq.resize((size_t)batch * pl[0].info.iq_samples_per_frame * sb);
+  int64_t done = 0;
+  while (!st && (frames < 0 || done < frames)) {
+    const int64_t want = frames >= 0 ? std::min<int64_t>(batch, frames - done) : batch;
+    // adapt until every PLP's queue covers the batch, or its file is used up
+    for (int k = 0; k < nplp && !st; k++) {
+      Plp &p = pl[k];
+      const int64_t if_bytes = p.info.ts_bytes_per_frame;   // BBFRAME bytes of one interleaving frame
+      while (!st && !p.done && (p.q_base + (int64_t)p.q.size()) / if_bytes * p.info.frames_per_if < done + want) {
+        while (!p.eof && (int64_t)p.win.size() < chunk) {
+          const size_t old = p.win.size();
+          p.win.resize((size_t)chunk);
+          const size_t got = std::fread(p.win.data() + old, 1, p.win.size() - old, p.f);
+          p.win.resize(old + got);
+          if (got == 0) p.eof = true;
+        }
+        const int64_t len = (int64_t)p.win.size() / 188 * 188;
+        dvbt2ll_modeadapt_result res;
+        if ((st = dvbt2ll_modeadapt_run_host(p.ad, p.win.data(), len, &p.pos, p.tmp.data(),
+                                             (int64_t)(p.tmp.size() / p.L), p.eof, &res)))
+          break;
+        int64_t *a = &p.tot.packets_in, *b = &res.packets_in;
+        for (int i = 0; i < 8; i++) a[i] += b[i];
+        p.q.insert(p.q.end(), p.tmp.begin(), p.tmp.begin() + (size_t)(res.bbframes * p.L));
+        p.win.erase(p.win.begin(), p.win.begin() + (size_t)(res.resume.ts_packet * 188));
+        p.pos = {0, res.resume.unit_byte, res.resume.dnp};
+        if (p.eof) p.done = true;   // flushed: nothing is left
+        else if (res.resume.ts_packet == 0 && res.bbframes == 0 && (int64_t)p.win.size() >= chunk) {
+          std::fprintf(stderr, "dvbt2ll_tx: PLP %d: no BBFRAME completes within %lld bytes of TS\n", k, (long long)chunk);
+          st = -1;
+        }
+      }
+    }
+    if (st) break;
+    int64_t n = want;
+    for (int k = 0; k < nplp; k++)
+      n = std::min<int64_t>(n, (pl[k].q_base + (int64_t)pl[k].q.size()) / pl[k].info.ts_bytes_per_frame *
+                                   pl[k].info.frames_per_if - done);
+    n = n / unit * unit;
+    if (n <= 0) break;
+    const void *ptr[DVBT2LL_MAX_PLP];
+    int64_t base[DVBT2LL_MAX_PLP], ql[DVBT2LL_MAX_PLP];
+    for (int k = 0; k < nplp; k++) { ptr[k] = pl[k].q.data(); base[k] = pl[k].q_base; ql[k] = (int64_t)pl[k].q.size(); }
+    if ((st = dvbt2ll_chain_run_plps_host(h, ptr, base, ql, done, (int)n, iq.data()))) break;
+    const size_t bytes = (size_t)n * pl[0].info.iq_samples_per_frame * sb;
+    if (std::fwrite(iq.data(), 1, bytes, fout) != bytes) { st = -1; break; }
+    done += n;
+    for (int k = 0; k < nplp; k++) {   // drop the interleaving frames no later T2 frame needs
+      const int64_t nb = done / pl[k].info.frames_per_if * pl[k].info.ts_bytes_per_frame;
+      pl[k].q.erase(pl[k].q.begin(), pl[k].q.begin() + (size_t)(nb - pl[k].q_base));
+      pl[k].q_base = nb;
+    }
+  }
+  if (st) std::fprintf(stderr, "dvbt2ll_tx: ts-npd run failed: %s\n", dvbt2ll_strerror(st));
+  std::fprintf(stderr, "dvbt2ll_tx: ts-npd: %lld T2 frames\n", (long long)done);
+  for (int k = 0; k < nplp; k++) {
+    const dvbt2ll_modeadapt_result &t = pl[k].tot;
+    std::fprintf(stderr, "dvbt2ll_tx: ts-npd: PLP %d: packets_in %lld, selected %lld, nulls_deleted %lld, nulls_kept %lld, "
+                 "nulls_dropped_at_flush %lld, sync_errors %lld, bbframes %lld, flushed %lld\n", k,
+                 (long long)t.packets_in, (long long)t.selected, (long long)t.nulls_deleted, (long long)t.nulls_kept,
+                 (long long)t.nulls_dropped_at_flush, (long long)t.sync_errors, (long long)t.bbframes,
+                 (long long)t.flushed);
+    if (pl[k].f) std::fclose(pl[k].f);
+    dvbt2ll_modeadapt_destroy(pl[k].ad);
+  }
+  if (fout && fout != stdout) std::fclose(fout);
+  return st ? 1 : 0;
+}
+
 // the multi-PLP transmitter: whole launch units per batch, each PLP's TS span from its own file
 int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const std::string &out_path, int fmt,
              float gain, int64_t frames, int batch, int device, bool print_params, int input = DVBT2LL_INPUT_TS,
-             int pid = 0, const std::vector<int> &plp_ids = {}) {
+             int pid = 0, const std::vector<int> &plp_ids = {}, const std::vector<std::vector<int>> &pids = {}) {
   dvbt2ll_mplp_chain_params p;
   std::memset(&p, 0, sizeof(p));
   dvbt2ll_mplp_params &m = p.fm;
@@ -318,7 +445,8 @@ int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const st
     std::printf(" %d\n", m.num_subslices);
     return 0;
   }
-  const bool t2mi = input == kInputT2mi;
+  const bool tsnpd = input == kInputTsNpd;
+  const bool t2mi = input == kInputT2mi || tsnpd;   // one file for all PLPs, the chain in BBFRAME input
   if ((int)ins.size() != (t2mi ? 1 : ps.nplp) || out_path.empty()) {
     std::fprintf(stderr, "dvbt2ll_tx: --mplp %s needs %d --in file(s) and --out\n", ps.name, t2mi ? 1 : ps.nplp);
     return 2;
@@ -336,7 +464,8 @@ int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const st
     return 1;
   }
   if (t2mi) {
-    const int rc = run_t2mi(h, ins[0], out_path, fmt, pid, plp_ids, frames, batch, device);
+    const int rc = tsnpd ? run_tsnpd(h, ins[0], out_path, fmt, pids, frames, batch, device)
+                         : run_t2mi(h, ins[0], out_path, fmt, pid, plp_ids, frames, batch, device);
     dvbt2ll_chain_destroy(h);
     return rc;
   }
@@ -396,6 +525,7 @@ int main(int argc, char **argv) {
   std::vector<std::string> sets, ins;
   int fmt = DVBT2LL_IQ_CF32, input = DVBT2LL_INPUT_TS, batch = 16, device = 0, pid = 4096;
   std::vector<int> plp_ids;
+  std::vector<std::vector<int>> pids;
   bool print_params = false;
   int64_t frames = -1;
   float gain = 1.f;
@@ -424,9 +554,19 @@ int main(int argc, char **argv) {
       if (v == "ts") input = DVBT2LL_INPUT_TS;
       else if (v == "bbframe") input = DVBT2LL_INPUT_BBFRAME;
       else if (v == "t2mi") input = kInputT2mi;
+      else if (v == "ts-npd") input = kInputTsNpd;
       else { std::fprintf(stderr, "dvbt2ll_tx: unknown input %s\n", v.c_str()); return 2; }
     } else if (a == "--pid") pid = (int)std::strtol(next(), nullptr, 0);
-    else if (a == "--plp-id") plp_ids.push_back((int)std::strtol(next(), nullptr, 0));
+    else if (a == "--pids") {
+      std::vector<int> one;
+      for (const char *c = next(); *c;) {
+        char *end;
+        one.push_back((int)std::strtol(c, &end, 0));
+        if (end == c) { std::fprintf(stderr, "dvbt2ll_tx: bad --pids list\n"); return 2; }
+        c = *end == ',' ? end + 1 : end;
+      }
+      pids.push_back(one);
+    } else if (a == "--plp-id") plp_ids.push_back((int)std::strtol(next(), nullptr, 0));
     else if (a == "--gain") gain = std::strtof(next(), nullptr);
     else if (a == "--frames") frames = std::strtoll(next(), nullptr, 10);
     else if (a == "--batch") batch = std::atoi(next());
@@ -439,7 +579,7 @@ int main(int argc, char **argv) {
     if (input == DVBT2LL_INPUT_BBFRAME) { std::fprintf(stderr, "dvbt2ll_tx: --input bbframe takes a single-PLP preset\n"); return 2; }
     for (auto &q : kMplpPresets)
       if (mplp == q.name)
-        return run_mplp(q, ins, out_path, fmt, gain, frames, batch, device, print_params, input, pid, plp_ids);
+        return run_mplp(q, ins, out_path, fmt, gain, frames, batch, device, print_params, input, pid, plp_ids, pids);
     std::fprintf(stderr, "dvbt2ll_tx: unknown multi-PLP preset %s\n", mplp.c_str());
     return 2;
   }
@@ -474,7 +614,8 @@ int main(int argc, char **argv) {
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: chain create: %s\n", dvbt2ll_strerror(st)); return 1; }
   dvbt2ll_chain_info info;
   // (the info after set_input: it then counts whole BBFRAMEs)
-  const bool t2mi = input == kInputT2mi;
+  const bool tsnpd = input == kInputTsNpd;
+  const bool t2mi = input == kInputT2mi || tsnpd;
   if ((st = dvbt2ll_chain_set_input(h, -1, t2mi ? DVBT2LL_INPUT_BBFRAME : input)) || (st = dvbt2ll_chain_get_info(h, &info)) ||
       (st = dvbt2ll_chain_set_output(h, gain, fmt))) {
     std::fprintf(stderr, "dvbt2ll_tx: %s\n", dvbt2ll_strerror(st));
@@ -482,7 +623,8 @@ int main(int argc, char **argv) {
     return 1;
   }
   if (t2mi) {
-    const int rc = run_t2mi(h, in_path, out_path, fmt, pid, plp_ids, frames, batch, device);
+    const int rc = tsnpd ? run_tsnpd(h, in_path, out_path, fmt, pids, frames, batch, device)
+                         : run_t2mi(h, in_path, out_path, fmt, pid, plp_ids, frames, batch, device);
     dvbt2ll_chain_destroy(h);
     return rc;
   }

@@ -17,6 +17,7 @@
 #include "../../include/dvbt2ll_hip.h"
 #include "t2_kernels.h"
 #include "t2_plan.h"
+#include "modeadapt_kernels.h"
 #include "t2mi_kernels.h"
 
 using namespace t2;
@@ -2018,3 +2019,156 @@ extern "C" int dvbt2ll_t2mi_run_host(dvbt2ll_t2mi *h, const void *ts, int64_t ts
 }
 
 extern "C" void dvbt2ll_t2mi_destroy(dvbt2ll_t2mi *h) { delete h; }
+
+// ============================================================================ mode adapter
+// A handle beside the chain, built like the T2-MI one: scratch sized at create from max_ts_bytes, no stream state, all
+// passes of a run on the caller's stream (modeadapt_kernels.hip), the result on the device until get_result.
+struct dvbt2ll_modeadapt {
+  DeviceCtx ctx;
+  dvbt2ll_modeadapt_params p{};
+  MaDev dev;
+  DevBuf scratch, ts_tmp, out_tmp;
+  hipEvent_t done = nullptr;     // the last run; a run on another stream waits for it (the scratch is shared)
+  hipStream_t last = nullptr;
+  bool ran = false;
+  ~dvbt2ll_modeadapt() {
+    if (done) { (void)hipSetDevice(ctx.device); (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+  }
+};
+
+// Kbch of (framesize, rate) as build_fec has them (t2_plan.cpp fec_numbers); 0: not a code
+static int modeadapt_kbch_of(int framesize, int rate) {
+  static const int normal[6] = {32208, 38688, 43040, 48408, 51648, 53840};
+  static const int shortf[8] = {7032, 9552, 10632, 11712, 12432, 13152, 5232, 6312};
+  if (framesize == 1) return rate >= 0 && rate < 6 ? normal[rate] : 0;
+  if (framesize == 0) return rate >= 0 && rate < 8 ? shortf[rate] : 0;
+  return 0;
+}
+
+// the resolved Kbch of the parameters, or 0 when they are refused
+static int modeadapt_params_kbch(const dvbt2ll_modeadapt_params &p) {
+  const int kbch = p.kbch ? p.kbch : modeadapt_kbch_of(p.framesize, p.rate);
+  if (kbch != 3072 && (kbch <= 0 || kbch % 8 || !t2mi_valid_len(kbch / 8))) return 0;
+  if ((p.sis_mis != 0 && p.sis_mis != 1) || p.isi < 0 || p.isi > 255) return 0;
+  if ((p.npd != 0 && p.npd != 1) || (p.pid_mask && !p.npd)) return 0;
+  if (p.max_ts_bytes < 188 || p.max_ts_bytes % 188 || p.max_ts_bytes >= ((int64_t)1 << 31)) return 0;
+  return kbch;
+}
+
+extern "C" int dvbt2ll_modeadapt_create(const dvbt2ll_modeadapt_params *p, int device, dvbt2ll_modeadapt **out) {
+  if (!p || !out) return DVBT2LL_EINVAL;
+  *out = nullptr;
+  const int kbch = modeadapt_params_kbch(*p);
+  if (!kbch) return DVBT2LL_EINVAL;
+  std::unique_ptr<dvbt2ll_modeadapt> h(new (std::nothrow) dvbt2ll_modeadapt());
+  if (!h) return DVBT2LL_ENOMEM;
+  h->p = *p;
+  h->p.kbch = kbch;
+  h->p.pid_mask = nullptr;   // copied to the device below: the caller's array is not kept
+  int r = h->ctx.init(device);
+  if (r) return r;
+  MaDev &d = h->dev;
+  d.npd = p->npd;
+  d.has_mask = p->pid_mask != nullptr;
+  d.L = (uint32_t)kbch / 8;
+  d.D = d.L - 10;
+  // MATYPE-1: TS_GS 11, SIS/MIS, CCM 1, ISSYI 0, NPD, EXT 00 (the chain's MATYPE_SIS / MATYPE_MIS with the NPD bit)
+  d.matype = (uint32_t)(p->sis_mis ? MATYPE_SIS : MATYPE_MIS | p->isi) | (p->npd ? 0x0400u : 0u);
+  d.max_ts = (uint32_t)(p->max_ts_bytes / 188);
+  if (h->scratch.ensure(modeadapt_layout(d, nullptr))) return DVBT2LL_ENOMEM;
+  (void)modeadapt_layout(d, h->scratch.p);
+  uint32_t tab[256];
+  modeadapt_host_table(tab);
+  HIP_TRY(hipMemcpy(d.crc, tab, sizeof tab, hipMemcpyHostToDevice));
+  if (p->pid_mask) HIP_TRY(hipMemcpy(d.mask, p->pid_mask, 1024, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d.res, 0, MA_R_WORDS * 8));
+  HIP_TRY(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+  *out = h.release();
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_modeadapt_params_from_chain(const dvbt2ll_chain *chain, int plp, dvbt2ll_modeadapt_params *p) {
+  if (!chain || !p || plp < 0 || plp >= chain->nplp) return DVBT2LL_EINVAL;
+  const auto &pl = *chain->plps[plp];
+  p->kbch = pl.fec.plan.kbch;
+  p->sis_mis = (pl.fec.dev.matype & 0x2000) ? 1 : 0;
+  p->isi = p->sis_mis ? 0 : (pl.fec.dev.matype & 255);
+  return DVBT2LL_OK;
+}
+
+static int modeadapt_run_args(const dvbt2ll_modeadapt *h, const void *ts, int64_t ts_len,
+                              const dvbt2ll_modeadapt_pos *start, void *out, int64_t cap, MaRun &r) {
+  if (!h || !ts || !start || !out) return DVBT2LL_EINVAL;
+  if (ts_len < 0 || ts_len % 188 || ts_len > h->p.max_ts_bytes || cap < 0) return DVBT2LL_EINVAL;
+  const int64_t n = ts_len / 188;
+  const int U = h->p.npd ? 188 : 187;
+  if (start->ts_packet < 0 || start->ts_packet > n || start->unit_byte < 0 || start->unit_byte >= U ||
+      start->dnp < 0 || start->dnp > 255 || (start->dnp && !h->p.npd))
+    return DVBT2LL_EINVAL;
+  if ((start->unit_byte || start->dnp) && start->ts_packet == n) return DVBT2LL_EINVAL;
+  r.ts = (const uint8_t *)ts;
+  r.i0 = (uint32_t)start->ts_packet;
+  r.n = (uint32_t)(n - start->ts_packet);
+  r.unit_byte = (uint32_t)start->unit_byte;
+  r.dnp = (uint32_t)start->dnp;
+  r.out = (uint8_t *)out;
+  r.cap = (uint32_t)std::min<int64_t>(cap, (int64_t)1 << 30);
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_modeadapt_run_device(dvbt2ll_modeadapt *h, const void *ts_dev, int64_t ts_len,
+                                            const dvbt2ll_modeadapt_pos *start, void *out_dev, int64_t out_cap_blocks,
+                                            int flush, void *stream) {
+  MaRun r;
+  int e = modeadapt_run_args(h, ts_dev, ts_len, start, out_dev, out_cap_blocks, r);
+  if (e) return e;
+  r.flush = flush != 0;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->ctx.stream;
+  if (h->ran && h->last != st) HIP_TRY(hipStreamWaitEvent(st, h->done, 0));
+  HIP_TRY(modeadapt_launch(h->dev, r, st));
+  HIP_TRY(hipEventRecord(h->done, st));
+  h->last = st;
+  h->ran = true;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_modeadapt_get_result(dvbt2ll_modeadapt *h, dvbt2ll_modeadapt_result *res) {
+  if (!h || !res) return DVBT2LL_EINVAL;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  uint64_t w[MA_R_WORDS];
+  HIP_TRY(hipMemcpy(w, h->dev.res, sizeof w, hipMemcpyDeviceToHost));
+  memset(res, 0, sizeof *res);
+  res->resume.ts_packet = (int64_t)w[MA_R_TS_PACKET];
+  res->resume.unit_byte = (int)w[MA_R_UNIT_BYTE];
+  res->resume.dnp = (int)w[MA_R_DNP];
+  int64_t *c = &res->packets_in;
+  for (int k = 0; k < 8; k++) c[k] = (int64_t)w[MA_R_PACKETS_IN + k];
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_modeadapt_run_host(dvbt2ll_modeadapt *h, const void *ts, int64_t ts_len,
+                                          const dvbt2ll_modeadapt_pos *start, void *out, int64_t out_cap_blocks,
+                                          int flush, dvbt2ll_modeadapt_result *res) {
+  MaRun r;
+  if (!res) return DVBT2LL_EINVAL;
+  int e = modeadapt_run_args(h, ts, ts_len, start, out, out_cap_blocks, r);
+  if (e) return e;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  // no more BBFRAMEs than the buffer's packets can fill, whatever the capacity says
+  const int64_t cap = std::min<int64_t>(r.cap, (int64_t)r.n * 188 / h->dev.D + 1);
+  if (h->ts_tmp.ensure((size_t)std::max<int64_t>(ts_len, 1))) return DVBT2LL_ENOMEM;
+  if (h->out_tmp.ensure((size_t)cap * h->dev.L + 16)) return DVBT2LL_ENOMEM;
+  if (ts_len) HIP_TRY(hipMemcpyAsync(h->ts_tmp.p, ts, (size_t)ts_len, hipMemcpyHostToDevice, h->ctx.stream));
+  if ((e = dvbt2ll_modeadapt_run_device(h, h->ts_tmp.p, ts_len, start, h->out_tmp.p, out_cap_blocks, flush,
+                                        h->ctx.stream)))
+    return e;
+  if ((e = dvbt2ll_modeadapt_get_result(h, res))) return e;
+  if (res->bbframes > 0)
+    HIP_TRY(hipMemcpy(out, h->out_tmp.p, (size_t)res->bbframes * h->dev.L, hipMemcpyDeviceToHost));
+  return DVBT2LL_OK;
+}
+
+extern "C" void dvbt2ll_modeadapt_destroy(dvbt2ll_modeadapt *h) { delete h; }

@@ -105,6 +105,21 @@ class _T2miResult(ctypes.Structure):
         "accepted")] + [("blocks", ctypes.c_int64 * MAX_PLP), ("by_type", ctypes.c_int64 * 256)]
 
 
+class _ModeAdaptParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("kbch", "framesize", "rate", "sis_mis", "isi", "npd")] + [
+        ("pid_mask", ctypes.c_void_p), ("max_ts_bytes", ctypes.c_int64)]
+
+
+class _ModeAdaptPos(ctypes.Structure):
+    _fields_ = [("ts_packet", ctypes.c_int64), ("unit_byte", ctypes.c_int), ("dnp", ctypes.c_int)]
+
+
+class _ModeAdaptResult(ctypes.Structure):
+    _fields_ = [("resume", _ModeAdaptPos)] + [(n, ctypes.c_int64) for n in (
+        "packets_in", "selected", "nulls_deleted", "nulls_kept", "nulls_dropped_at_flush", "sync_errors", "bbframes",
+        "flushed")]
+
+
 BLOCKS = ("bbheaderbch", "ldpc", "interleavermod", "framemapperfint", "pilotgenp1insert")
 PARAMS = {"bbheaderbch": _BbParams, "ldpc": _LdpcParams, "interleavermod": _ImParams,
           "framemapperfint": _FmParams, "pilotgenp1insert": _PgParams}
@@ -128,6 +143,8 @@ EXPORTS += ["dvbt2ll_chain_" + f for f in ("create_miso_pair", "create_mplp_miso
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("set_input", "get_input", "bbheader_errors")]
 EXPORTS += ["dvbt2ll_t2mi_" + f for f in ("create", "params_from_chain", "run_device", "get_result", "get_packets",
                                           "run_host", "destroy")]
+EXPORTS += ["dvbt2ll_modeadapt_" + f for f in ("create", "params_from_chain", "run_device", "get_result", "run_host",
+                                               "destroy")]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create", "get_info", "run_device", "run_streams", "run_host", "set_output", "set_slots", "set_graph", "set_timing",
                                            "get_timing", "debug_codewords", "debug_cell_pairs", "debug_cells",
                                            "synchronize", "sync_errors",
@@ -226,6 +243,14 @@ def lib():
                                         ctypes.POINTER(i64), ctypes.POINTER(_T2miResult)]
     L.dvbt2ll_t2mi_destroy.argtypes = [vp]
     L.dvbt2ll_t2mi_destroy.restype = None
+    L.dvbt2ll_modeadapt_create.argtypes = [ctypes.POINTER(_ModeAdaptParams), ci, ctypes.POINTER(vp)]
+    L.dvbt2ll_modeadapt_params_from_chain.argtypes = [vp, ci, ctypes.POINTER(_ModeAdaptParams)]
+    L.dvbt2ll_modeadapt_run_device.argtypes = [vp, vp, i64, ctypes.POINTER(_ModeAdaptPos), vp, i64, ci, vp]
+    L.dvbt2ll_modeadapt_get_result.argtypes = [vp, ctypes.POINTER(_ModeAdaptResult)]
+    L.dvbt2ll_modeadapt_run_host.argtypes = [vp, vp, i64, ctypes.POINTER(_ModeAdaptPos), vp, i64, ci,
+                                             ctypes.POINTER(_ModeAdaptResult)]
+    L.dvbt2ll_modeadapt_destroy.argtypes = [vp]
+    L.dvbt2ll_modeadapt_destroy.restype = None
     L.dvbt2ll_chain_destroy.argtypes = [vp]
     L.dvbt2ll_chain_destroy.restype = None
     _lib = L

@@ -523,6 +523,92 @@ int dvbt2ll_t2mi_run_host(dvbt2ll_t2mi *h, const void *ts, int64_t ts_len, const
 void dvbt2ll_t2mi_destroy(dvbt2ll_t2mi *h);
 
 /* ---------------------------------------------------------------------------
+ * Mode adapter (EN 302 755 5.1.4, 5.1.7): a device buffer of 188-byte TS packets -> one PLP's packed BBFRAMEs in
+ * high-efficiency mode, with null-packet deletion and an optional PID selection, in the layout
+ * DVBT2LL_INPUT_BBFRAME reads (L = kbch / 8 bytes per BBFRAME, back to back).  A handle of its own beside the chain:
+ * it holds scratch, no stream state, and composes with every run form.  Scope: high-efficiency mode only (no sync
+ * byte, no CRC-8 in the stream; UPL = SYNC = 0).  Not built: null-packet deletion in normal mode, ISSY (ISCR / BUFS
+ * / TTO), in-band type A, GSE, the common PLP.  With npd = 0 the output is the reference's HEM BBFRAME stream of the
+ * same TS byte for byte (in-band off); the reference sets NPD = 0 (lib/bbheaderbch_bb_impl.cc:272-325), so npd = 1 is
+ * PARITY UNPINNED, pinned by tests/modeadapt_ref.py's sequential restatement and its receiver.
+ *
+ * input      whole 188-byte packets; a length that is not a multiple of 188 is refused before any launch.
+ * classes    npd = 1: a packet is selected when its PID is in pid_mask (NULL: every PID) and is not 0x1FFF; every
+ *            other packet is null.  npd = 0: every packet is selected (a mask is refused: without deletion the
+ *            unselected packets have nowhere to go).  A first byte other than 0x47 is counted in sync_errors and the
+ *            packet is otherwise treated normally (bbheaderbch_bb_impl.cc:675).
+ * DNP        (npd = 1) the nulls of a maximal run are numbered r = 0, 1, ...; the null with r % 256 == 255 is kept:
+ *            it is transmitted as a user packet holding the null packet (47 1F FF 10, 184 x FF, whatever the packet
+ *            held: another PLP's bytes never leak), and the count restarts after it.  Every other null is deleted.
+ *            A transmitted packet's DNP byte is the number of nulls deleted since the previous transmitted packet:
+ *            255 for a kept null, n % 256 for a selected packet after a run of n nulls.
+ * units      each transmitted packet contributes its bytes 1 .. 187 (the sync byte is dropped), then with npd = 1
+ *            its DNP byte: units of U = 188 (npd = 1) or 187 (npd = 0) bytes, back to back.
+ * BBFRAMEs   D = (kbch - 80) / 8 data-field bytes each; BBFRAME k's data field is unit-stream bytes [k D, (k + 1) D).
+ *            Header: MATYPE-1 = TS_GS 11, SIS/MIS, CCM 1, ISSYI 0, NPD = npd, EXT 00; MATYPE-2 = the ISI (MIS) or 0;
+ *            UPL 0; DFL 8 D; SYNC 0; SYNCD = 8 x the bytes from the data field's start to the first unit that begins
+ *            in it (0 when one begins at byte 0, 0xFFFF when none does); CRC-8 XOR 1 (MODE = high efficiency), the
+ *            byte the chain's own HEM header has: dvbt2ll_chain_bbheader_errors counts none.
+ * capacity   a call emits the largest number of whole BBFRAMEs that the input and out_cap_blocks allow, and returns
+ *            resume = {ts_packet, unit_byte, dnp}: the index, in this call's buffer, of the transmitted packet whose
+ *            unit holds the first unit-stream byte not emitted, how many of that unit's bytes were emitted, and that
+ *            unit's DNP.  If the emitted bytes end exactly with the call's last unit, resume is the packet after the
+ *            last transmitted one (the call's start packet when none was) with unit_byte = dnp = 0: trailing nulls
+ *            are seen again, as the start of a run.  The next call passes resume as start, with a buffer that begins
+ *            at or before that packet (start.ts_packet = its index there).  A start with unit_byte > 0 or dnp > 0
+ *            makes that packet transmitted unconditionally with that DNP (it may be a kept null) and must name a
+ *            packet of the buffer.  Chained calls at any split produce the single call's bytes, and their counters
+ *            add up.
+ * flush      flush = 1 is honoured when the whole BBFRAMEs and the flush frame fit out_cap_blocks: one more BBFRAME
+ *            carries the remaining bytes (DFL = 8 x their count, SYNCD by the rule above, the rest of the data field
+ *            zero; none when nothing remains), the nulls after the last transmitted packet are dropped and counted
+ *            in nulls_dropped_at_flush (not in nulls_deleted), and resume is {packets of the buffer, 0, 0}.
+ * counters   cover exactly the packets from start.ts_packet to before resume.ts_packet; bbframes includes the flush
+ *            frame, flushed is 1 when one was written.
+ * bounds     nothing outside [ts_dev, ts_dev + ts_len) is read, nothing outside out_cap_blocks BBFRAMEs of out_dev
+ *            is written.
+ * ------------------------------------------------------------------------- */
+typedef struct dvbt2ll_modeadapt dvbt2ll_modeadapt;
+typedef struct {
+  int kbch;                              /* a T2 code's Kbch: one of the chain's 14, or 3072 (short 1/4, which the
+                                            chain does not encode); 0: taken from framesize / rate */
+  int framesize, rate;                   /* FECFRAME_* / C*: used when kbch == 0 */
+  int sis_mis;                           /* 1: single input stream; 0: multiple, MATYPE-2 = isi (0 .. 255) */
+  int isi;
+  int npd;                               /* 0 / 1 */
+  const uint8_t *pid_mask;               /* NULL, or 1024 bytes: PID p is bit p & 7 of byte p >> 3 (copied at create) */
+  int64_t max_ts_bytes;                  /* largest ts_len of a run, a multiple of 188 below 2^31 */
+} dvbt2ll_modeadapt_params;
+typedef struct {
+  int64_t ts_packet;                     /* a packet index in [0, ts_len / 188] */
+  int unit_byte;                         /* 0 .. U - 1 bytes of that packet's unit already emitted */
+  int dnp;                               /* 0 .. 255: that unit's DNP (0 with npd = 0) */
+} dvbt2ll_modeadapt_pos;
+typedef struct {
+  dvbt2ll_modeadapt_pos resume;
+  int64_t packets_in, selected, nulls_deleted, nulls_kept, nulls_dropped_at_flush, sync_errors, bbframes, flushed;
+} dvbt2ll_modeadapt_result;
+int dvbt2ll_modeadapt_create(const dvbt2ll_modeadapt_params *p, int device, dvbt2ll_modeadapt **out);
+/* fills kbch, sis_mis and isi from the chain's PLP plp (a multi-PLP chain's headers say MIS with ISI = the PLP's
+ * index); the other fields stay */
+int dvbt2ll_modeadapt_params_from_chain(const dvbt2ll_chain *chain, int plp, dvbt2ll_modeadapt_params *p);
+/* ts_dev: ts_len bytes (a multiple of 188, <= max_ts_bytes) on the device; start: {0, 0, 0} or a previous call's
+ * resume position in this buffer's packet indices; out_dev: room for out_cap_blocks BBFRAMEs of kbch / 8 bytes.
+ * Asynchronous on stream (NULL: the handle's own); no host round trip.  One run of a handle at a time: the next run
+ * call on another stream first waits for the previous one.  DVBT2LL_EINVAL, nothing launched: ts_len not a multiple
+ * of 188 or above max_ts_bytes, start outside the buffer, unit_byte outside 0 .. U - 1, dnp outside 0 .. 255 (or not 0
+ * with npd = 0), unit_byte > 0 or dnp > 0 at the buffer's end, a negative capacity, a null pointer. */
+int dvbt2ll_modeadapt_run_device(dvbt2ll_modeadapt *h, const void *ts_dev, int64_t ts_len,
+                                 const dvbt2ll_modeadapt_pos *start, void *out_dev, int64_t out_cap_blocks, int flush,
+                                 void *stream);
+/* synchronises with the last run and returns its result */
+int dvbt2ll_modeadapt_get_result(dvbt2ll_modeadapt *h, dvbt2ll_modeadapt_result *res);
+/* host buffers, synchronous: the TS is copied in, the written BBFRAMEs are copied out */
+int dvbt2ll_modeadapt_run_host(dvbt2ll_modeadapt *h, const void *ts, int64_t ts_len, const dvbt2ll_modeadapt_pos *start,
+                               void *out, int64_t out_cap_blocks, int flush, dvbt2ll_modeadapt_result *res);
+void dvbt2ll_modeadapt_destroy(dvbt2ll_modeadapt *h);
+
+/* ---------------------------------------------------------------------------
  * ABI version.  The parameter and info structs are passed by pointer with no size field, so a caller
  * compiled against another layout would be read or written past its struct.  Version history:
  *   1  rounds 1-4: dvbt2ll_plp_params = the first nine ints, no num_subslices, no frames_per_if;
