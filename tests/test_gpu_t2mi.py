@@ -30,11 +30,24 @@ def _deframer(plps=C.PLPS1, max_ts_bytes=188 * 256, max_packets=256, **kw):
     return dvbt2ll.T2miDeframer(C.PID, plps=plps, max_ts_bytes=max_ts_bytes, max_packets=max_packets, **kw)
 
 
+_STREAM = []
+
+
+def _side_stream():
+    """a torch stream with a handle of its own: torch's default stream has handle 0, which the C ABI reads as "the
+    handle's own stream" (a non-blocking one), and then the fills and the copy of the TS below and the deframer's
+    kernels would not be ordered -- with a TS of a hundred megabytes the deframer reads it half copied"""
+    import torch
+    if not _STREAM:
+        _STREAM.append(torch.cuda.Stream())
+    return _STREAM[0]
+
+
 def device_run(de, ts, start=(0, 0), caps=None, misalign=3, stream=None, full_blocks=8):
     """one run_device with everything inside poisoned arrays; returns the result with bbframes filled in, after
     checking the guards.  caps None: room for full_blocks blocks per output"""
     import torch
-    st = torch.cuda.current_stream() if stream is None else stream
+    st = _side_stream() if stream is None else stream
     caps = [full_blocks] * de.nplp if caps is None else list(caps)
     with torch.cuda.stream(st):
         buf = torch.full((2 * GUARD + len(ts) + 16,), POISON, dtype=torch.uint8, device="cuda")

@@ -6,8 +6,9 @@ frames, the arms alternating, all in one process.  Run three processes and put t
   python tools/modeadapt_measure.py --cfg cfg3 --frames 1280 --chunk-frames 160 --reps 5
 
 The TS is one chunk's packets (seeded payloads, every tenth a null packet) repeated on the GPU side: every chunk lies
-in memory of its own, each call adapts one chunk from a fresh start, and the first call's output is compared with the
-sequential reference of tests/modeadapt_ref.py over its first BBFRAMEs.  Prints one JSON line."""
+in memory of its own, each call adapts one chunk from a fresh start, and before anything is timed one call's whole
+output, counters and resume position are compared with tests/large_ref.py's adapt_fast (the vectorised restatement
+that tests/test_cpu_large_ref.py proves against the sequential reference).  Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -31,7 +32,7 @@ def main():
     import torch
     import dvbt2ll
     from dvbt2ll.configs import CONFIGS, KBCH, ts_packets
-    import modeadapt_ref as R
+    import large_ref as G
 
     assert torch.cuda.is_available(), "needs a GPU"
     cfg = CONFIGS[a.cfg]
@@ -83,9 +84,10 @@ def main():
     copy()
     res = ad.result()
     assert res.counters["bbframes"] == cf * F, res.counters
-    head = 64
-    ref = R.adapt(ts1[:188 * (head * D // 188 * 10 // 9 + 20)], kbch, cap=head)
-    assert np.array_equal(out[(nchunks - 1) * ob:(nchunks - 1) * ob + head * L].cpu().numpy(), ref.bbframes)
+    # the last call's whole output, counters and resume position against the vectorised reference
+    ref = G.adapt_fast(ts1, kbch, cap=cf * F)
+    assert np.array_equal(out[(nchunks - 1) * ob:].cpu().numpy(), ref.bbframes)
+    assert res.counters == ref.counters and tuple(res.resume) == tuple(ref.resume), (res, ref.counters, ref.resume)
     t_ad, t_cp = [], []
     for _ in range(a.reps):
         t_ad.append(timed(adapt))
