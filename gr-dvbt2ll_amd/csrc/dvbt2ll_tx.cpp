@@ -24,6 +24,12 @@
 // flushed at the end of the file): --pids a,b,... selects the PLP's PIDs (default: every PID but 0x1FFF).  With
 // --mplp presets the one --in file feeds every PLP, each through an adapter of its own: repeat --pids per PLP.
 //
+// --input ule reads IP datagrams (records of a 16-bit big-endian length and that many PDU bytes) and wraps them on the
+// GPU in ULE SNDUs packed into TS packets of --pid (RFC 4326; dvbt2ll_ule_run_host in chunks, continued from each
+// call's resume position, flushed at the end of the file): the reference flowgraph's ule_source.  --mac sets the
+// destination address (default 02:00:48:55:4c:4b), --no-dest sends none (D = 1), --packing 0 starts a packet per
+// SNDU.  The TS then goes through the chain's TS input exactly as a TS file does.
+//
 // --mplp runs a multi-PLP frame preset (one TS file per PLP, dvbt2ll_chain_create_mplp / _run_plps_host;
 // batches are whole launch units, dvbt2ll_chain_unit_frames).
 //
@@ -93,13 +99,18 @@ void usage(FILE *f) {
                "                          inputmode reservedbiasbits l1scrambled inband; pilotgen:\n"
                "                          misogroup equalization bandwidth; bbheaderbch: tsrate)\n"
                "                          misogroup: 0 TX1, 1 TX2 (pilots only), 2 TX2 with MISO processing\n"
-               "  --input ts|bbframe|t2mi|ts-npd what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
+               "  --input ts|bbframe|t2mi|ts-npd|ule what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
                "                          of kbch / 8 bytes each (single-PLP presets), or a TS carrying T2-MI\n"
                "                          (one file; single-PLP and --mplp presets)\n"
                "                          ts-npd: a TS adapted on the GPU to HEM BBFRAMEs with null-packet deletion\n"
+               "                          ule: records of a 16-bit big-endian length and an IP datagram, wrapped on\n"
+               "                          the GPU in ULE SNDUs (RFC 4326) on --pid (single-PLP presets)\n"
+               "  --mac aa:bb:cc:dd:ee:ff --input ule: the destination address (default 02:00:48:55:4c:4b)\n"
+               "  --no-dest               --input ule: SNDUs without a destination address (D = 1)\n"
+               "  --packing 0|1           --input ule: pack SNDUs back to back (default 1) or one per packet start\n"
                "  --pids A,B,...          --input ts-npd: the PIDs of the next PLP of the preset (repeat per PLP;\n"
                "                          default: every PID but 0x1FFF)\n"
-               "  --pid N                 --input t2mi: the PID of the T2-MI stream (default 4096)\n"
+               "  --pid N                 --input t2mi / ule: the PID of the T2-MI stream / of the SNDUs (default 4096)\n"
                "  --plp-id K              --input t2mi: the PLP_ID feeding the next PLP of the preset (repeat per\n"
                "                          PLP; default 0, 1, ...)\n"
                "  --format cf32|sc16      IQ sample format (default cf32, pilotgen's complex64)\n"
@@ -418,6 +429,84 @@ int run_tsnpd(dvbt2ll_chain *h, const std::string &in_path, const std::string &o
   return st ? 1 : 0;
 }
 
+constexpr int kInputUle = 4;   // --input ule (the chain itself runs in DVBT2LL_INPUT_TS)
+
+// --input ule: the file's length-prefixed PDUs -> the ULE encapsulator in chunks -> a temporary TS file, which the
+// caller reads as it reads a TS file.  Returns the file rewound, or nullptr.
+FILE *run_ule(const std::string &in_path, int pid, int d_bit, const uint8_t *dest, int packing, int device) {
+  const size_t chunk = 4 << 20, max_pdus = 65536;   // PDU bytes and PDUs per encapsulator call
+  dvbt2ll_ule_params up;
+  std::memset(&up, 0, sizeof(up));
+  up.pid = pid;
+  up.d_bit = d_bit;
+  std::memcpy(up.dest, dest, 6);
+  up.packing = packing;
+  up.max_pdu_bytes = (int64_t)chunk + 65536;
+  up.max_pdus = (int)max_pdus;
+  dvbt2ll_ule *enc = nullptr;
+  int st = dvbt2ll_ule_create(&up, device, &enc);
+  if (st) { std::fprintf(stderr, "dvbt2ll_tx: ule: %s\n", dvbt2ll_strerror(st)); return nullptr; }
+  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
+  FILE *ts = std::tmpfile();
+  if (!fin || !ts) {
+    std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : "a temporary file", std::strerror(errno));
+    dvbt2ll_ule_destroy(enc);
+    return nullptr;
+  }
+  std::vector<uint8_t> pdus, out;
+  std::vector<uint32_t> off(1, 0);
+  dvbt2ll_ule_pos pos = {0, 0, 0};
+  dvbt2ll_ule_result tot;
+  std::memset(&tot, 0, sizeof(tot));
+  bool eof = false;
+  while (!st) {
+    while (!eof && pdus.size() < chunk && off.size() <= max_pdus) {
+      uint8_t lb[2];
+      if (std::fread(lb, 1, 2, fin) != 2) { eof = true; break; }
+      const size_t len = ((size_t)lb[0] << 8) | lb[1], old = pdus.size();
+      pdus.resize(old + len);
+      if (len && std::fread(pdus.data() + old, 1, len, fin) != len) { pdus.resize(old); eof = true; break; }   // a cut record
+      off.push_back((uint32_t)pdus.size());
+    }
+    const int64_t n = (int64_t)off.size() - 1;
+    // the records lie side by side in pdus, so this many packets hold them all
+    const int64_t cap = packing ? ((int64_t)pdus.size() + 14 * n) / 182 + 2 : ((int64_t)pdus.size() + 14 * n) / 184 + n + 1;
+    out.resize((size_t)cap * 188);
+    const uint8_t none = 0;
+    dvbt2ll_ule_result res;
+    if ((st = dvbt2ll_ule_run_host(enc, pdus.empty() ? &none : pdus.data(), (int64_t)pdus.size(), off.data(), nullptr, n,
+                                   &pos, out.data(), cap, eof, &res)))
+      break;
+    int64_t *a = &tot.pdus_in, *b = &res.pdus_in;
+    for (int i = 0; i < 8; i++) a[i] += b[i];
+    if (res.ts_packets && std::fwrite(out.data(), 188, (size_t)res.ts_packets, ts) != (size_t)res.ts_packets) { st = -1; break; }
+    // continue from the resume position: drop the PDUs before it
+    const uint32_t cut = off[(size_t)res.resume.pdu];
+    pdus.erase(pdus.begin(), pdus.begin() + cut);
+    off.erase(off.begin(), off.begin() + (size_t)res.resume.pdu);
+    for (uint32_t &o : off) o -= cut;
+    pos = {0, res.resume.sndu_byte, res.resume.cc};
+    if (eof) break;
+    // nothing consumed and no room to read on (a short datagram with max_pdus skipped records behind it holds its
+    // open packet back for ever): give up, not loop
+    if (res.resume.pdu == 0 && res.ts_packets == 0 && (pdus.size() >= chunk || off.size() > max_pdus)) {
+      std::fprintf(stderr, "dvbt2ll_tx: ule: no packet completes within %zu bytes / %zu records\n", pdus.size(), off.size() - 1);
+      st = -1;
+      break;
+    }
+  }
+  if (st) std::fprintf(stderr, "dvbt2ll_tx: ule run failed: %s\n", dvbt2ll_strerror(st));
+  std::fprintf(stderr, "dvbt2ll_tx: ule: pdus_in %lld, sndus %lld, skipped_len %lld, skipped_type %lld, ts_packets %lld, "
+               "pusi_packets %lld, pad_bytes %lld, flushed %lld\n", (long long)tot.pdus_in, (long long)tot.sndus,
+               (long long)tot.skipped_len, (long long)tot.skipped_type, (long long)tot.ts_packets,
+               (long long)tot.pusi_packets, (long long)tot.pad_bytes, (long long)tot.flushed);
+  if (fin != stdin) std::fclose(fin);
+  dvbt2ll_ule_destroy(enc);
+  if (st) { std::fclose(ts); return nullptr; }
+  std::rewind(ts);
+  return ts;
+}
+
 // the multi-PLP transmitter: whole launch units per batch, each PLP's TS span from its own file
 int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const std::string &out_path, int fmt,
              float gain, int64_t frames, int batch, int device, bool print_params, int input = DVBT2LL_INPUT_TS,
@@ -526,6 +615,8 @@ int main(int argc, char **argv) {
   int fmt = DVBT2LL_IQ_CF32, input = DVBT2LL_INPUT_TS, batch = 16, device = 0, pid = 4096;
   std::vector<int> plp_ids;
   std::vector<std::vector<int>> pids;
+  uint8_t mac[6] = {0x02, 0x00, 0x48, 0x55, 0x4C, 0x4B};   // the flowgraph's ule_source
+  int ule_d_bit = 0, ule_packing = 1;
   bool print_params = false;
   int64_t frames = -1;
   float gain = 1.f;
@@ -555,6 +646,7 @@ int main(int argc, char **argv) {
       else if (v == "bbframe") input = DVBT2LL_INPUT_BBFRAME;
       else if (v == "t2mi") input = kInputT2mi;
       else if (v == "ts-npd") input = kInputTsNpd;
+      else if (v == "ule") input = kInputUle;
       else { std::fprintf(stderr, "dvbt2ll_tx: unknown input %s\n", v.c_str()); return 2; }
     } else if (a == "--pid") pid = (int)std::strtol(next(), nullptr, 0);
     else if (a == "--pids") {
@@ -566,7 +658,16 @@ int main(int argc, char **argv) {
         c = *end == ',' ? end + 1 : end;
       }
       pids.push_back(one);
-    } else if (a == "--plp-id") plp_ids.push_back((int)std::strtol(next(), nullptr, 0));
+    } else if (a == "--mac") {
+      unsigned m[6];
+      if (std::sscanf(next(), "%2x:%2x:%2x:%2x:%2x:%2x", &m[0], &m[1], &m[2], &m[3], &m[4], &m[5]) != 6) {
+        std::fprintf(stderr, "dvbt2ll_tx: bad --mac\n");
+        return 2;
+      }
+      for (int k = 0; k < 6; k++) mac[k] = (uint8_t)m[k];
+    } else if (a == "--no-dest") ule_d_bit = 1;
+    else if (a == "--packing") ule_packing = std::atoi(next());
+    else if (a == "--plp-id") plp_ids.push_back((int)std::strtol(next(), nullptr, 0));
     else if (a == "--gain") gain = std::strtof(next(), nullptr);
     else if (a == "--frames") frames = std::strtoll(next(), nullptr, 10);
     else if (a == "--batch") batch = std::atoi(next());
@@ -576,7 +677,10 @@ int main(int argc, char **argv) {
   }
 
   if (!mplp.empty()) {
-    if (input == DVBT2LL_INPUT_BBFRAME) { std::fprintf(stderr, "dvbt2ll_tx: --input bbframe takes a single-PLP preset\n"); return 2; }
+    if (input == DVBT2LL_INPUT_BBFRAME || input == kInputUle) {
+      std::fprintf(stderr, "dvbt2ll_tx: --input bbframe / ule takes a single-PLP preset\n");
+      return 2;
+    }
     for (auto &q : kMplpPresets)
       if (mplp == q.name)
         return run_mplp(q, ins, out_path, fmt, gain, frames, batch, device, print_params, input, pid, plp_ids, pids);
@@ -614,8 +718,9 @@ int main(int argc, char **argv) {
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: chain create: %s\n", dvbt2ll_strerror(st)); return 1; }
   dvbt2ll_chain_info info;
   // (the info after set_input: it then counts whole BBFRAMEs)
-  const bool tsnpd = input == kInputTsNpd;
+  const bool tsnpd = input == kInputTsNpd, ule = input == kInputUle;
   const bool t2mi = input == kInputT2mi || tsnpd;
+  if (ule) input = DVBT2LL_INPUT_TS;   // the encapsulator's TS is read as a TS file is
   if ((st = dvbt2ll_chain_set_input(h, -1, t2mi ? DVBT2LL_INPUT_BBFRAME : input)) || (st = dvbt2ll_chain_get_info(h, &info)) ||
       (st = dvbt2ll_chain_set_output(h, gain, fmt))) {
     std::fprintf(stderr, "dvbt2ll_tx: %s\n", dvbt2ll_strerror(st));
@@ -628,7 +733,12 @@ int main(int argc, char **argv) {
     dvbt2ll_chain_destroy(h);
     return rc;
   }
-  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
+  FILE *fin = ule ? run_ule(in_path, pid, ule_d_bit, mac, ule_packing, device)
+                  : in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
+  if (ule && !fin) {
+    dvbt2ll_chain_destroy(h);
+    return 1;
+  }
   FILE *fout = out_path == "-" ? stdout : std::fopen(out_path.c_str(), "wb");
   if (!fin || !fout) {
     std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : out_path.c_str(),

@@ -120,6 +120,20 @@ class _ModeAdaptResult(ctypes.Structure):
         "flushed")]
 
 
+class _UleParams(ctypes.Structure):
+    _fields_ = [("pid", ctypes.c_int), ("d_bit", ctypes.c_int), ("dest", ctypes.c_uint8 * 6),
+                ("packing", ctypes.c_int), ("max_pdu_bytes", ctypes.c_int64), ("max_pdus", ctypes.c_int)]
+
+
+class _UlePos(ctypes.Structure):
+    _fields_ = [("pdu", ctypes.c_int64), ("sndu_byte", ctypes.c_int), ("cc", ctypes.c_int)]
+
+
+class _UleResult(ctypes.Structure):
+    _fields_ = [("resume", _UlePos)] + [(n, ctypes.c_int64) for n in (
+        "pdus_in", "sndus", "skipped_len", "skipped_type", "ts_packets", "pusi_packets", "pad_bytes", "flushed")]
+
+
 BLOCKS = ("bbheaderbch", "ldpc", "interleavermod", "framemapperfint", "pilotgenp1insert")
 PARAMS = {"bbheaderbch": _BbParams, "ldpc": _LdpcParams, "interleavermod": _ImParams,
           "framemapperfint": _FmParams, "pilotgenp1insert": _PgParams}
@@ -145,6 +159,7 @@ EXPORTS += ["dvbt2ll_t2mi_" + f for f in ("create", "params_from_chain", "run_de
                                           "run_host", "destroy")]
 EXPORTS += ["dvbt2ll_modeadapt_" + f for f in ("create", "params_from_chain", "run_device", "get_result", "run_host",
                                                "destroy")]
+EXPORTS += ["dvbt2ll_ule_" + f for f in ("create", "run_device", "get_result", "run_host", "destroy")]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create", "get_info", "run_device", "run_streams", "run_host", "set_output", "set_slots", "set_graph", "set_timing",
                                            "get_timing", "debug_codewords", "debug_cell_pairs", "debug_cells",
                                            "synchronize", "sync_errors",
@@ -251,6 +266,13 @@ def lib():
                                              ctypes.POINTER(_ModeAdaptResult)]
     L.dvbt2ll_modeadapt_destroy.argtypes = [vp]
     L.dvbt2ll_modeadapt_destroy.restype = None
+    L.dvbt2ll_ule_create.argtypes = [ctypes.POINTER(_UleParams), ci, ctypes.POINTER(vp)]
+    L.dvbt2ll_ule_run_device.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(_UlePos), vp, i64, ci, vp]
+    L.dvbt2ll_ule_get_result.argtypes = [vp, ctypes.POINTER(_UleResult)]
+    L.dvbt2ll_ule_run_host.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(_UlePos), vp, i64, ci,
+                                       ctypes.POINTER(_UleResult)]
+    L.dvbt2ll_ule_destroy.argtypes = [vp]
+    L.dvbt2ll_ule_destroy.restype = None
     L.dvbt2ll_chain_destroy.argtypes = [vp]
     L.dvbt2ll_chain_destroy.restype = None
     _lib = L

@@ -609,6 +609,98 @@ int dvbt2ll_modeadapt_run_host(dvbt2ll_modeadapt *h, const void *ts, int64_t ts_
 void dvbt2ll_modeadapt_destroy(dvbt2ll_modeadapt *h);
 
 /* ---------------------------------------------------------------------------
+ * ULE encapsulator (RFC 4326): a device buffer of PDUs (IP datagrams) and a device offset table -> 188-byte TS
+ * packets that the chain's TS input, the mode adapter and dvbt2ll_tx take as they are: the data path of the
+ * reference flowgraph's source block (gr-ule's ule_source in apps/vv009-4kshort.grc).  A handle of its own beside the
+ * chain: it holds scratch, no stream state.  Not built: ULE extension headers and bridged frames (Type is an opaque
+ * 16-bit field), per-PDU destination addresses, adaptation-field stuffing, GSE, the TAP interface, PSI / SI.
+ * gr-ule is not part of the reference tree, so all of this is PARITY UNPINNED, pinned by tests/ule_ref.py's
+ * sequential restatement and its RFC 4326 section 7 receiver.
+ *
+ * input      pdu_dev holds pdu_len bytes (below 2^31); off_dev holds n_pdus + 1 uint32_t offsets: PDU i is bytes
+ *            [off[i], off[i + 1]).  type_dev is optional: n_pdus uint16_t Type fields.  With type_dev == NULL the
+ *            Type comes from the PDU's first nibble: 4 -> 0x0800, 6 -> 0x86DD; any other nibble: the PDU is skipped
+ *            and counted in skipped_type.  A PDU is skipped and counted in skipped_len when off[i + 1] <= off[i],
+ *            or off[i + 1] > pdu_len, or the SNDU Length would exceed 32767 (the length is judged first: such a PDU
+ *            is never counted in skipped_type).  A skipped PDU contributes nothing; every rule below speaks of the
+ *            remaining (valid) PDUs only.  Nothing outside [pdu_dev, pdu_dev + pdu_len) and the two tables is read,
+ *            whatever the offsets say.  The offsets need not ascend: valid PDUs may overlap or repeat, each is
+ *            encapsulated as it stands, and the packets may then be more than the buffer's bytes suggest.
+ * SNDU       (RFC 4326 section 4) in order: the D bit (d_bit); Length, 15 bits: the bytes after the Type field up to
+ *            and including the CRC = (d_bit ? 0 : 6) + pdu_bytes + 4; Type, 16 bits; the 6-byte destination address
+ *            dest when d_bit == 0; the PDU; CRC-32 (polynomial 0x04C11DB7, initial value 0xFFFFFFFF, no reflection,
+ *            no final XOR: the CRC the T2-MI deframer checks) over every SNDU byte before it, big-endian.  The SNDU
+ *            has n = 4 + Length bytes; the smallest has 9.
+ * TS packets sync 47, TEI 0, PUSI, priority 0, pid, scrambling 00, adaptation field control 01; the continuity
+ *            counter is start.cc, plus one mod 16 per emitted packet; 184 payload bytes.  With PUSI = 1 the first
+ *            payload byte is the Payload Pointer PP: the payload bytes between it and the first SNDU that starts in
+ *            the packet.
+ * packing=1  when a packet begins, R is the number of bytes of the current SNDU not yet sent (0: the packet begins
+ *            with a new SNDU); "next": another valid SNDU follows in this call.
+ *              R >= 184: PUSI 0, 184 SNDU bytes.   R = 183: PUSI 0, 183 bytes, FF.   R = 182: PUSI 0, 182 bytes,
+ *              FF FF (the End Indicator).
+ *              R <= 181 and next: PUSI 1, PP = R, the R bytes, then SNDUs back to back: a new SNDU starts while at
+ *              least 2 payload bytes are free and next exists (one that does not fit runs on into the following
+ *              packets, to which this list applies again); an SNDU ending with exactly 1 byte free is followed by FF
+ *              and the packet is closed; one ending on the last byte closes the packet.
+ *              0 < R <= 181, no next, flush = 1: PUSI 0, R bytes, the rest FF.   R = 0, no next: no packet.
+ *              A PUSI packet left with free bytes and no next: with flush = 1 it is filled with FF (the first two are
+ *              the End Indicator); without flush it is not emitted.
+ * packing=0  one SNDU per packet start.  R = 0: PUSI 1, PP 0, up to 183 SNDU bytes, the rest FF.  R > 0: PUSI 0,
+ *            min(R, 184) bytes, the rest FF.  Every packet is determined by its own SNDU; flush changes nothing
+ *            except flushed.
+ * capacity   a call emits the longest prefix of determined packets that fits out_cap_packets and returns resume =
+ *            {pdu, sndu_byte, cc}: the index of the PDU whose SNDU holds the first SNDU byte not emitted, how many of
+ *            that SNDU's bytes were emitted, the counter of the next packet; {n_pdus, 0, cc} when nothing is left.
+ *            The next call passes resume as start, with a PDU list that begins at or before that PDU.  A start with
+ *            sndu_byte > 0 begins with R = n - sndu_byte of that SNDU, whose CRC is computed again (a sndu_byte that
+ *            is not below n, or at a skipped PDU, is taken as 0).  Chained calls at any split produce the single
+ *            call's bytes.
+ * counters   pdus_in, sndus, skipped_len, skipped_type cover the PDUs from start.pdu to before resume.pdu, so they
+ *            add up over chained calls; ts_packets, pusi_packets and pad_bytes (the FF bytes; a PP is none) cover the
+ *            packets emitted; flushed is 1 when flush was set and nothing is left.
+ * bounds     nothing outside out_cap_packets x 188 bytes of out_dev is written.
+ * ------------------------------------------------------------------------- */
+typedef struct dvbt2ll_ule dvbt2ll_ule;
+typedef struct {
+  int pid;                               /* 0 .. 0x1FFE */
+  int d_bit;                             /* 0: every SNDU carries dest; 1: none does */
+  uint8_t dest[6];                       /* the destination address (the flowgraph's 02:00:48:55:4c:4b) */
+  int packing;                           /* 0 / 1 */
+  int64_t max_pdu_bytes;                 /* largest pdu_len of a run, 1 .. 2^31 - 1 */
+  int max_pdus;                          /* largest n_pdus of a run, 1 .. 2^24 */
+} dvbt2ll_ule_params;
+typedef struct {
+  int64_t pdu;                           /* a PDU index in [0, n_pdus] */
+  int sndu_byte;                         /* bytes of that PDU's SNDU already emitted */
+  int cc;                                /* 0 .. 15: the next packet's continuity counter */
+} dvbt2ll_ule_pos;
+typedef struct {
+  dvbt2ll_ule_pos resume;
+  int64_t pdus_in, sndus, skipped_len, skipped_type, ts_packets, pusi_packets, pad_bytes, flushed;
+} dvbt2ll_ule_result;
+/* DVBT2LL_EINVAL: a null pointer, pid / d_bit / packing / the maxima out of range; DVBT2LL_EDEVICE without a GPU */
+int dvbt2ll_ule_create(const dvbt2ll_ule_params *p, int device, dvbt2ll_ule **out);
+/* pdu_dev, off_dev, type_dev (or NULL) on the device; start: {0, 0, cc} or a previous call's resume position in this
+ * list's PDU indices; out_dev: room for out_cap_packets x 188 bytes.  Asynchronous on stream (NULL: the handle's
+ * own); no host round trip.  One run of a handle at a time: the next run call on another stream first waits for the
+ * previous one.  DVBT2LL_EINVAL, nothing launched: a null pointer (type_dev may be), pdu_len or n_pdus negative or
+ * above the create-time maxima, a negative capacity, start.pdu outside [0, n_pdus], sndu_byte negative or > 0 at
+ * n_pdus, cc outside 0 .. 15. */
+int dvbt2ll_ule_run_device(dvbt2ll_ule *h, const void *pdu_dev, int64_t pdu_len, const uint32_t *off_dev,
+                           const uint16_t *type_dev, int64_t n_pdus, const dvbt2ll_ule_pos *start, void *out_dev,
+                           int64_t out_cap_packets, int flush, void *stream);
+/* synchronises with the last run and returns its result */
+int dvbt2ll_ule_get_result(dvbt2ll_ule *h, dvbt2ll_ule_result *res);
+/* host buffers, synchronous: the PDUs and tables are copied in, the written packets are copied out.  The device
+ * output buffer holds out_cap_packets, or what n_pdus PDUs inside pdu_len bytes can become at the most if that is
+ * less. */
+int dvbt2ll_ule_run_host(dvbt2ll_ule *h, const void *pdu, int64_t pdu_len, const uint32_t *off, const uint16_t *type,
+                         int64_t n_pdus, const dvbt2ll_ule_pos *start, void *out, int64_t out_cap_packets, int flush,
+                         dvbt2ll_ule_result *res);
+void dvbt2ll_ule_destroy(dvbt2ll_ule *h);
+
+/* ---------------------------------------------------------------------------
  * ABI version.  The parameter and info structs are passed by pointer with no size field, so a caller
  * compiled against another layout would be read or written past its struct.  Version history:
  *   1  rounds 1-4: dvbt2ll_plp_params = the first nine ints, no num_subslices, no frames_per_if;
