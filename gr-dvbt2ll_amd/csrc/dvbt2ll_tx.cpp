@@ -30,6 +30,11 @@
 // destination address (default 02:00:48:55:4c:4b), --no-dest sends none (D = 1), --packing 0 starts a packet per
 // SNDU.  The TS then goes through the chain's TS input exactly as a TS file does.
 //
+// --input gse reads the same records and wraps them on the GPU in GSE packets laid into normal-mode BBFRAMEs (TS 102
+// 606-1; dvbt2ll_gse_run_host in chunks, continued from each call's resume position, flushed at the end of the file).
+// --label / --label3 / --no-label choose the 6-byte, 3-byte or no label.  The BBFRAMEs then go through the chain's
+// BBFRAME input exactly as a BBFRAME file does.
+//
 // --mplp runs a multi-PLP frame preset (one TS file per PLP, dvbt2ll_chain_create_mplp / _run_plps_host;
 // batches are whole launch units, dvbt2ll_chain_unit_frames).
 //
@@ -99,12 +104,16 @@ void usage(FILE *f) {
                "                          inputmode reservedbiasbits l1scrambled inband; pilotgen:\n"
                "                          misogroup equalization bandwidth; bbheaderbch: tsrate)\n"
                "                          misogroup: 0 TX1, 1 TX2 (pilots only), 2 TX2 with MISO processing\n"
-               "  --input ts|bbframe|t2mi|ts-npd|ule what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
+               "  --input ts|bbframe|t2mi|ts-npd|ule|gse what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
                "                          of kbch / 8 bytes each (single-PLP presets), or a TS carrying T2-MI\n"
                "                          (one file; single-PLP and --mplp presets)\n"
                "                          ts-npd: a TS adapted on the GPU to HEM BBFRAMEs with null-packet deletion\n"
                "                          ule: records of a 16-bit big-endian length and an IP datagram, wrapped on\n"
                "                          the GPU in ULE SNDUs (RFC 4326) on --pid (single-PLP presets)\n"
+               "                          gse: the same records, wrapped on the GPU in GSE packets (TS 102 606-1) in\n"
+               "                          normal-mode BBFRAMEs (single-PLP presets)\n"
+               "  --label aa:bb:cc:dd:ee:ff | --label3 aa:bb:cc | --no-label\n"
+               "                          --input gse: the 6-byte label (default 02:00:48:55:4c:4b), a 3-byte one, none\n"
                "  --mac aa:bb:cc:dd:ee:ff --input ule: the destination address (default 02:00:48:55:4c:4b)\n"
                "  --no-dest               --input ule: SNDUs without a destination address (D = 1)\n"
                "  --packing 0|1           --input ule: pack SNDUs back to back (default 1) or one per packet start\n"
@@ -507,6 +516,84 @@ FILE *run_ule(const std::string &in_path, int pid, int d_bit, const uint8_t *des
   return ts;
 }
 
+constexpr int kInputGse = 5;   // --input gse (the chain itself runs in DVBT2LL_INPUT_BBFRAME)
+
+// --input gse: the file's length-prefixed PDUs -> the GSE encapsulator in chunks -> a temporary file of BBFRAMEs, which
+// the caller reads as it reads a BBFRAME file.  Returns the file rewound, or nullptr.
+FILE *run_gse(const dvbt2ll_chain *chain, const std::string &in_path, int label_len, const uint8_t *label, int device) {
+  const size_t chunk = 4 << 20, max_pdus = 65536;   // PDU bytes and PDUs per encapsulator call
+  dvbt2ll_gse_params gp;
+  std::memset(&gp, 0, sizeof(gp));
+  int st = dvbt2ll_gse_params_from_chain(chain, 0, &gp);
+  gp.label_len = label_len;
+  std::memcpy(gp.label, label, 6);
+  gp.max_pdu_bytes = (int64_t)chunk + 65536;
+  gp.max_pdus = (int)max_pdus;
+  dvbt2ll_gse *enc = nullptr;
+  if (!st) st = dvbt2ll_gse_create(&gp, device, &enc);
+  if (st) { std::fprintf(stderr, "dvbt2ll_tx: gse: %s\n", dvbt2ll_strerror(st)); return nullptr; }
+  const int64_t Lb = gp.kbch / 8, D = Lb - 10;
+  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
+  FILE *bb = std::tmpfile();
+  if (!fin || !bb) {
+    std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : "a temporary file", std::strerror(errno));
+    dvbt2ll_gse_destroy(enc);
+    return nullptr;
+  }
+  std::vector<uint8_t> pdus, out;
+  std::vector<uint32_t> off(1, 0);
+  dvbt2ll_gse_pos pos = {0, 0, 0};
+  dvbt2ll_gse_result tot;
+  std::memset(&tot, 0, sizeof(tot));
+  bool eof = false;
+  while (!st) {
+    while (!eof && pdus.size() < chunk && off.size() <= max_pdus) {
+      uint8_t lb[2];
+      if (std::fread(lb, 1, 2, fin) != 2) { eof = true; break; }
+      const size_t len = ((size_t)lb[0] << 8) | lb[1], old = pdus.size();
+      pdus.resize(old + len);
+      if (len && std::fread(pdus.data() + old, 1, len, fin) != len) { pdus.resize(old); eof = true; break; }   // a cut record
+      off.push_back((uint32_t)pdus.size());
+    }
+    const int64_t n = (int64_t)off.size() - 1;
+    // the records lie side by side in pdus, so this many frames hold them all
+    const int64_t cap = ((int64_t)pdus.size() + (4 + label_len) * n) / (D - 14 - label_len) + 2;
+    out.resize((size_t)(cap * Lb));
+    const uint8_t none = 0;
+    dvbt2ll_gse_result res;
+    if ((st = dvbt2ll_gse_run_host(enc, pdus.empty() ? &none : pdus.data(), (int64_t)pdus.size(), off.data(), nullptr, n,
+                                   &pos, out.data(), cap, eof, &res)))
+      break;
+    int64_t *a = &tot.pdus_in, *b = &res.pdus_in;
+    for (int i = 0; i < 9; i++) a[i] += b[i];
+    if (res.bbframes && std::fwrite(out.data(), (size_t)Lb, (size_t)res.bbframes, bb) != (size_t)res.bbframes) { st = -1; break; }
+    // continue from the resume position: drop the PDUs before it
+    const uint32_t cut = off[(size_t)res.resume.pdu];
+    pdus.erase(pdus.begin(), pdus.begin() + cut);
+    off.erase(off.begin(), off.begin() + (size_t)res.resume.pdu);
+    for (uint32_t &o : off) o -= cut;
+    pos = {0, res.resume.pdu_byte, res.resume.frag_id};
+    if (eof) break;
+    // nothing consumed and no room to read on (a short datagram with max_pdus skipped records behind it holds its
+    // open frame back for ever): give up, not loop
+    if (res.resume.pdu == 0 && res.bbframes == 0 && (pdus.size() >= chunk || off.size() > max_pdus)) {
+      std::fprintf(stderr, "dvbt2ll_tx: gse: no frame completes within %zu bytes / %zu records\n", pdus.size(), off.size() - 1);
+      st = -1;
+      break;
+    }
+  }
+  if (st) std::fprintf(stderr, "dvbt2ll_tx: gse run failed: %s\n", dvbt2ll_strerror(st));
+  std::fprintf(stderr, "dvbt2ll_tx: gse: pdus_in %lld, complete %lld, fragmented %lld, gse_packets %lld, skipped_len %lld, "
+               "skipped_type %lld, bbframes %lld, pad_bytes %lld, flushed %lld\n", (long long)tot.pdus_in,
+               (long long)tot.complete, (long long)tot.fragmented, (long long)tot.gse_packets, (long long)tot.skipped_len,
+               (long long)tot.skipped_type, (long long)tot.bbframes, (long long)tot.pad_bytes, (long long)tot.flushed);
+  if (fin != stdin) std::fclose(fin);
+  dvbt2ll_gse_destroy(enc);
+  if (st) { std::fclose(bb); return nullptr; }
+  std::rewind(bb);
+  return bb;
+}
+
 // the multi-PLP transmitter: whole launch units per batch, each PLP's TS span from its own file
 int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const std::string &out_path, int fmt,
              float gain, int64_t frames, int batch, int device, bool print_params, int input = DVBT2LL_INPUT_TS,
@@ -617,6 +704,8 @@ int main(int argc, char **argv) {
   std::vector<std::vector<int>> pids;
   uint8_t mac[6] = {0x02, 0x00, 0x48, 0x55, 0x4C, 0x4B};   // the flowgraph's ule_source
   int ule_d_bit = 0, ule_packing = 1;
+  uint8_t gse_label[6] = {0x02, 0x00, 0x48, 0x55, 0x4C, 0x4B};
+  int gse_label_len = 6;
   bool print_params = false;
   int64_t frames = -1;
   float gain = 1.f;
@@ -647,6 +736,7 @@ int main(int argc, char **argv) {
       else if (v == "t2mi") input = kInputT2mi;
       else if (v == "ts-npd") input = kInputTsNpd;
       else if (v == "ule") input = kInputUle;
+      else if (v == "gse") input = kInputGse;
       else { std::fprintf(stderr, "dvbt2ll_tx: unknown input %s\n", v.c_str()); return 2; }
     } else if (a == "--pid") pid = (int)std::strtol(next(), nullptr, 0);
     else if (a == "--pids") {
@@ -665,7 +755,17 @@ int main(int argc, char **argv) {
         return 2;
       }
       for (int k = 0; k < 6; k++) mac[k] = (uint8_t)m[k];
-    } else if (a == "--no-dest") ule_d_bit = 1;
+    } else if (a == "--label" || a == "--label3") {
+      unsigned m[6] = {};
+      const int want = a == "--label" ? 6 : 3;
+      if (std::sscanf(next(), "%2x:%2x:%2x:%2x:%2x:%2x", &m[0], &m[1], &m[2], &m[3], &m[4], &m[5]) != want) {
+        std::fprintf(stderr, "dvbt2ll_tx: bad %s\n", a.c_str());
+        return 2;
+      }
+      for (int k = 0; k < 6; k++) gse_label[k] = (uint8_t)m[k];
+      gse_label_len = want;
+    } else if (a == "--no-label") gse_label_len = 0;
+    else if (a == "--no-dest") ule_d_bit = 1;
     else if (a == "--packing") ule_packing = std::atoi(next());
     else if (a == "--plp-id") plp_ids.push_back((int)std::strtol(next(), nullptr, 0));
     else if (a == "--gain") gain = std::strtof(next(), nullptr);
@@ -677,8 +777,8 @@ int main(int argc, char **argv) {
   }
 
   if (!mplp.empty()) {
-    if (input == DVBT2LL_INPUT_BBFRAME || input == kInputUle) {
-      std::fprintf(stderr, "dvbt2ll_tx: --input bbframe / ule takes a single-PLP preset\n");
+    if (input == DVBT2LL_INPUT_BBFRAME || input == kInputUle || input == kInputGse) {
+      std::fprintf(stderr, "dvbt2ll_tx: --input bbframe / ule / gse takes a single-PLP preset\n");
       return 2;
     }
     for (auto &q : kMplpPresets)
@@ -718,9 +818,10 @@ int main(int argc, char **argv) {
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: chain create: %s\n", dvbt2ll_strerror(st)); return 1; }
   dvbt2ll_chain_info info;
   // (the info after set_input: it then counts whole BBFRAMEs)
-  const bool tsnpd = input == kInputTsNpd, ule = input == kInputUle;
+  const bool tsnpd = input == kInputTsNpd, ule = input == kInputUle, gse = input == kInputGse;
   const bool t2mi = input == kInputT2mi || tsnpd;
   if (ule) input = DVBT2LL_INPUT_TS;   // the encapsulator's TS is read as a TS file is
+  if (gse) input = DVBT2LL_INPUT_BBFRAME;   // the encapsulator's BBFRAMEs are read as a BBFRAME file is
   if ((st = dvbt2ll_chain_set_input(h, -1, t2mi ? DVBT2LL_INPUT_BBFRAME : input)) || (st = dvbt2ll_chain_get_info(h, &info)) ||
       (st = dvbt2ll_chain_set_output(h, gain, fmt))) {
     std::fprintf(stderr, "dvbt2ll_tx: %s\n", dvbt2ll_strerror(st));
@@ -734,8 +835,9 @@ int main(int argc, char **argv) {
     return rc;
   }
   FILE *fin = ule ? run_ule(in_path, pid, ule_d_bit, mac, ule_packing, device)
+                  : gse ? run_gse(h, in_path, gse_label_len, gse_label, device)
                   : in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
-  if (ule && !fin) {
+  if ((ule || gse) && !fin) {
     dvbt2ll_chain_destroy(h);
     return 1;
   }

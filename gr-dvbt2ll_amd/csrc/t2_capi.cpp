@@ -19,6 +19,7 @@
 #include "t2_plan.h"
 #include "modeadapt_kernels.h"
 #include "ule_kernels.h"
+#include "gse_kernels.h"
 #include "t2mi_kernels.h"
 
 using namespace t2;
@@ -2308,3 +2309,158 @@ extern "C" int dvbt2ll_ule_run_host(dvbt2ll_ule *h, const void *pdu, int64_t pdu
 }
 
 extern "C" void dvbt2ll_ule_destroy(dvbt2ll_ule *h) { delete h; }
+
+// ============================================================================ GSE encapsulator
+// A handle beside the chain, built like the ULE one: scratch sized at create from max_pdus and Kbch, no stream state,
+// all passes of a run on the caller's stream (gse_kernels.hip), the result on the device until get_result.
+struct dvbt2ll_gse {
+  DeviceCtx ctx;
+  dvbt2ll_gse_params p{};
+  GseDev dev;
+  DevBuf scratch, pdu_tmp, off_tmp, type_tmp, out_tmp;
+  hipEvent_t done = nullptr;     // the last run; a run on another stream waits for it (the scratch is shared)
+  hipStream_t last = nullptr;
+  bool ran = false;
+  ~dvbt2ll_gse() {
+    if (done) { (void)hipSetDevice(ctx.device); (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+  }
+};
+
+// the resolved Kbch of the parameters, or 0 when they are refused
+static int gse_params_kbch(const dvbt2ll_gse_params &p) {
+  const int kbch = p.kbch ? p.kbch : modeadapt_kbch_of(p.framesize, p.rate);
+  // 58192 (D = 7264) is the DVB family's largest Kbch; no T2 code has it, the chain takes no such frame.  It is
+  // accepted so that the position tables are pinned at the largest state count the entry format is sized for
+  if (kbch != 3072 && kbch != 58192 && (kbch <= 0 || kbch % 8 || !t2mi_valid_len(kbch / 8))) return 0;
+  if ((p.sis_mis != 0 && p.sis_mis != 1) || p.isi < 0 || p.isi > 255) return 0;
+  if (p.label_len != 0 && p.label_len != 3 && p.label_len != 6) return 0;
+  if (p.max_pdu_bytes < 1 || p.max_pdu_bytes >= ((int64_t)1 << 31)) return 0;
+  if (p.max_pdus < 1 || p.max_pdus > (1 << 24)) return 0;   // 2^24 PDUs of 13 frames: below 2^32 frames
+  return kbch;
+}
+
+extern "C" int dvbt2ll_gse_create(const dvbt2ll_gse_params *p, int device, dvbt2ll_gse **out) {
+  if (!p || !out) return DVBT2LL_EINVAL;
+  *out = nullptr;
+  const int kbch = gse_params_kbch(*p);
+  if (!kbch) return DVBT2LL_EINVAL;
+  std::unique_ptr<dvbt2ll_gse> h(new (std::nothrow) dvbt2ll_gse());
+  if (!h) return DVBT2LL_ENOMEM;
+  h->p = *p;
+  h->p.kbch = kbch;
+  int r = h->ctx.init(device);
+  if (r) return r;
+  GseDev &d = h->dev;
+  d.Lb = (uint32_t)kbch / 8;
+  d.D = d.Lb - 10;
+  d.L = (uint32_t)p->label_len;
+  d.lt = d.L == 6 ? 0 : d.L == 3 ? 1 : 2;
+  memcpy(d.label, p->label, 6);
+  // MATYPE-1: TS_GS 10, SIS/MIS, CCM 1, ISSYI 0, NPD 0, EXT 00
+  d.matype = p->sis_mis ? 0xB000u : 0x9000u | (uint32_t)p->isi;
+  d.max_pdus = (uint32_t)p->max_pdus;
+  if (h->scratch.ensure(gse_layout(d, nullptr))) return DVBT2LL_ENOMEM;
+  (void)gse_layout(d, h->scratch.p);
+  std::vector<uint32_t> tab(GSE_TAB_WORDS);
+  gse_host_tables(tab.data());
+  HIP_TRY(hipMemcpy(d.tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d.res, 0, (GSE_R_WORDS + 2) * 8));
+  HIP_TRY(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+  *out = h.release();
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_gse_params_from_chain(const dvbt2ll_chain *chain, int plp, dvbt2ll_gse_params *p) {
+  if (!chain || !p || plp < 0 || plp >= chain->nplp) return DVBT2LL_EINVAL;
+  const auto &pl = *chain->plps[plp];
+  p->kbch = pl.fec.plan.kbch;
+  p->sis_mis = (pl.fec.dev.matype & 0x2000) ? 1 : 0;
+  p->isi = p->sis_mis ? 0 : (pl.fec.dev.matype & 255);
+  return DVBT2LL_OK;
+}
+
+static int gse_run_args(const dvbt2ll_gse *h, const void *pdu, int64_t pdu_len, const uint32_t *off,
+                        const uint16_t *type, int64_t n_pdus, const dvbt2ll_gse_pos *start, void *out, int64_t cap,
+                        GseRun &r) {
+  if (!h || !pdu || !off || !start || !out) return DVBT2LL_EINVAL;
+  if (pdu_len < 0 || pdu_len > h->p.max_pdu_bytes || n_pdus < 0 || n_pdus > h->p.max_pdus || cap < 0)
+    return DVBT2LL_EINVAL;
+  if (start->pdu < 0 || start->pdu > n_pdus || start->pdu_byte < 0 || start->frag_id < 0 ||
+      start->frag_id > 255)
+    return DVBT2LL_EINVAL;
+  r.pdu = (const uint8_t *)pdu;
+  r.pdu_len = (uint32_t)pdu_len;
+  r.off = off;
+  r.type = type;
+  r.i0 = (uint32_t)start->pdu;
+  r.n = (uint32_t)(n_pdus - start->pdu);
+  r.pdu_byte = (uint32_t)start->pdu_byte;
+  r.frag_id = (uint32_t)start->frag_id;
+  r.out = (uint8_t *)out;
+  r.cap = (uint32_t)std::min<int64_t>(cap, (int64_t)1 << 30);
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_gse_run_device(dvbt2ll_gse *h, const void *pdu_dev, int64_t pdu_len, const uint32_t *off_dev,
+                                      const uint16_t *type_dev, int64_t n_pdus, const dvbt2ll_gse_pos *start,
+                                      void *out_dev, int64_t out_cap_blocks, int flush, void *stream) {
+  GseRun r;
+  int e = gse_run_args(h, pdu_dev, pdu_len, off_dev, type_dev, n_pdus, start, out_dev, out_cap_blocks, r);
+  if (e) return e;
+  r.flush = flush != 0;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->ctx.stream;
+  if (h->ran && h->last != st) HIP_TRY(hipStreamWaitEvent(st, h->done, 0));
+  HIP_TRY(gse_launch(h->dev, r, st));
+  HIP_TRY(hipEventRecord(h->done, st));
+  h->last = st;
+  h->ran = true;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_gse_get_result(dvbt2ll_gse *h, dvbt2ll_gse_result *res) {
+  if (!h || !res) return DVBT2LL_EINVAL;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  uint64_t w[GSE_R_WORDS];
+  HIP_TRY(hipMemcpy(w, h->dev.res, sizeof w, hipMemcpyDeviceToHost));
+  memset(res, 0, sizeof *res);
+  res->resume.pdu = (int64_t)w[GSE_R_PDU];
+  res->resume.pdu_byte = (int)w[GSE_R_PDU_BYTE];
+  res->resume.frag_id = (int)w[GSE_R_FRAG_ID];
+  int64_t *c = &res->pdus_in;
+  for (int k = 0; k < 9; k++) c[k] = (int64_t)w[GSE_R_PDUS_IN + k];
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_gse_run_host(dvbt2ll_gse *h, const void *pdu, int64_t pdu_len, const uint32_t *off,
+                                    const uint16_t *type, int64_t n_pdus, const dvbt2ll_gse_pos *start, void *out,
+                                    int64_t out_cap_blocks, int flush, dvbt2ll_gse_result *res) {
+  GseRun r;
+  if (!res) return DVBT2LL_EINVAL;
+  int e = gse_run_args(h, pdu, pdu_len, off, type, n_pdus, start, out, out_cap_blocks, r);
+  if (e) return e;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  // no more frames than the PDUs can become wherever the offsets put them, whatever the capacity says: the device
+  // buffer holds this capacity, and this capacity is what the run is given
+  const int64_t cap = (int64_t)std::min<uint64_t>(r.cap, gse_frame_limit(h->dev, r.pdu_len, r.n));
+  if (h->pdu_tmp.ensure((size_t)std::max<int64_t>(pdu_len, 1))) return DVBT2LL_ENOMEM;
+  if (h->off_tmp.ensure((size_t)(n_pdus + 1) * 4)) return DVBT2LL_ENOMEM;
+  if (type && h->type_tmp.ensure((size_t)std::max<int64_t>(n_pdus, 1) * 2)) return DVBT2LL_ENOMEM;
+  if (h->out_tmp.ensure((size_t)cap * h->dev.Lb + 16)) return DVBT2LL_ENOMEM;
+  hipStream_t st = h->ctx.stream;
+  if (pdu_len) HIP_TRY(hipMemcpyAsync(h->pdu_tmp.p, pdu, (size_t)pdu_len, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->off_tmp.p, off, (size_t)(n_pdus + 1) * 4, hipMemcpyHostToDevice, st));
+  if (type && n_pdus) HIP_TRY(hipMemcpyAsync(h->type_tmp.p, type, (size_t)n_pdus * 2, hipMemcpyHostToDevice, st));
+  if ((e = dvbt2ll_gse_run_device(h, h->pdu_tmp.p, pdu_len, (const uint32_t *)h->off_tmp.p,
+                                  type ? (const uint16_t *)h->type_tmp.p : nullptr, n_pdus, start, h->out_tmp.p,
+                                  cap, flush, st)))
+    return e;
+  if ((e = dvbt2ll_gse_get_result(h, res))) return e;
+  if (res->bbframes > 0)
+    HIP_TRY(hipMemcpy(out, h->out_tmp.p, (size_t)res->bbframes * h->dev.Lb, hipMemcpyDeviceToHost));
+  return DVBT2LL_OK;
+}
+
+extern "C" void dvbt2ll_gse_destroy(dvbt2ll_gse *h) { delete h; }

@@ -12,6 +12,7 @@ from .chain import Chain, IQ_CF32, IQ_SC16, INPUT_TS, INPUT_BBFRAME  # noqa: F40
 from .t2mi import T2miDeframer, T2miResult  # noqa: F401
 from .modeadapt import ModeAdapter, ModeAdaptPos, ModeAdaptResult  # noqa: F401
 from .ule import UleEncapsulator, UlePos, UleResult  # noqa: F401
+from .gse import GseEncapsulator, GsePos, GseResult  # noqa: F401
 from .configs import CONFIGS, T2Config, ts_packets, ts_for_frames, bbframe_span  # noqa: F401
 from .configs import MPLP_CONFIGS, MplpConfig, PlpConfig  # noqa: F401
 from .configs import MISO_TX2_PROCESSED  # noqa: F401

@@ -134,6 +134,22 @@ class _UleResult(ctypes.Structure):
         "pdus_in", "sndus", "skipped_len", "skipped_type", "ts_packets", "pusi_packets", "pad_bytes", "flushed")]
 
 
+class _GseParams(ctypes.Structure):
+    _fields_ = [("kbch", ctypes.c_int), ("framesize", ctypes.c_int), ("rate", ctypes.c_int),
+                ("sis_mis", ctypes.c_int), ("isi", ctypes.c_int), ("label_len", ctypes.c_int),
+                ("label", ctypes.c_uint8 * 6), ("max_pdu_bytes", ctypes.c_int64), ("max_pdus", ctypes.c_int)]
+
+
+class _GsePos(ctypes.Structure):
+    _fields_ = [("pdu", ctypes.c_int64), ("pdu_byte", ctypes.c_int), ("frag_id", ctypes.c_int)]
+
+
+class _GseResult(ctypes.Structure):
+    _fields_ = [("resume", _GsePos)] + [(n, ctypes.c_int64) for n in (
+        "pdus_in", "complete", "fragmented", "gse_packets", "skipped_len", "skipped_type", "bbframes", "pad_bytes",
+        "flushed")]
+
+
 BLOCKS = ("bbheaderbch", "ldpc", "interleavermod", "framemapperfint", "pilotgenp1insert")
 PARAMS = {"bbheaderbch": _BbParams, "ldpc": _LdpcParams, "interleavermod": _ImParams,
           "framemapperfint": _FmParams, "pilotgenp1insert": _PgParams}
@@ -148,6 +164,8 @@ EXPORTS += ["dvbt2ll_framemapperfint_stream_items", "dvbt2ll_pilotgenp1insert_ac
 EXPORTS += ["dvbt2ll_bbheaderbch_set_isi"]
 EXPORTS += ["dvbt2ll_framemapper_mplp_" + f for f in ("create", "output_multiple", "stream_items", "forecast",
                                                       "general_work", "destroy")]
+EXPORTS += ["dvbt2ll_gse_" + f for f in ("create", "params_from_chain", "run_device", "get_result", "run_host",
+                                         "destroy")]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("host_submit", "host_wait", "run_host_pipelined", "run_plps_host")]
 EXPORTS += ["dvbt2ll_host_alloc", "dvbt2ll_host_free"]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create_mplp", "num_plps", "unit_frames", "get_plp_info", "run_plps",
@@ -273,6 +291,14 @@ def lib():
                                        ctypes.POINTER(_UleResult)]
     L.dvbt2ll_ule_destroy.argtypes = [vp]
     L.dvbt2ll_ule_destroy.restype = None
+    L.dvbt2ll_gse_create.argtypes = [ctypes.POINTER(_GseParams), ci, ctypes.POINTER(vp)]
+    L.dvbt2ll_gse_params_from_chain.argtypes = [vp, ci, ctypes.POINTER(_GseParams)]
+    L.dvbt2ll_gse_run_device.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(_GsePos), vp, i64, ci, vp]
+    L.dvbt2ll_gse_get_result.argtypes = [vp, ctypes.POINTER(_GseResult)]
+    L.dvbt2ll_gse_run_host.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(_GsePos), vp, i64, ci,
+                                       ctypes.POINTER(_GseResult)]
+    L.dvbt2ll_gse_destroy.argtypes = [vp]
+    L.dvbt2ll_gse_destroy.restype = None
     L.dvbt2ll_chain_destroy.argtypes = [vp]
     L.dvbt2ll_chain_destroy.restype = None
     _lib = L

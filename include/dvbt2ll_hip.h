@@ -528,7 +528,7 @@ void dvbt2ll_t2mi_destroy(dvbt2ll_t2mi *h);
  * DVBT2LL_INPUT_BBFRAME reads (L = kbch / 8 bytes per BBFRAME, back to back).  A handle of its own beside the chain:
  * it holds scratch, no stream state, and composes with every run form.  Scope: high-efficiency mode only (no sync
  * byte, no CRC-8 in the stream; UPL = SYNC = 0).  Not built: null-packet deletion in normal mode, ISSY (ISCR / BUFS
- * / TTO), in-band type A, GSE, the common PLP.  With npd = 0 the output is the reference's HEM BBFRAME stream of the
+ * / TTO), in-band type A, the common PLP (GSE: dvbt2ll_gse_* below).  With npd = 0 the output is the reference's HEM BBFRAME stream of the
  * same TS byte for byte (in-band off); the reference sets NPD = 0 (lib/bbheaderbch_bb_impl.cc:272-325), so npd = 1 is
  * PARITY UNPINNED, pinned by tests/modeadapt_ref.py's sequential restatement and its receiver.
  *
@@ -613,7 +613,8 @@ void dvbt2ll_modeadapt_destroy(dvbt2ll_modeadapt *h);
  * packets that the chain's TS input, the mode adapter and dvbt2ll_tx take as they are: the data path of the
  * reference flowgraph's source block (gr-ule's ule_source in apps/vv009-4kshort.grc).  A handle of its own beside the
  * chain: it holds scratch, no stream state.  Not built: ULE extension headers and bridged frames (Type is an opaque
- * 16-bit field), per-PDU destination addresses, adaptation-field stuffing, GSE, the TAP interface, PSI / SI.
+ * 16-bit field), per-PDU destination addresses, adaptation-field stuffing, the TAP interface, PSI / SI (GSE:
+ * dvbt2ll_gse_* below).
  * gr-ule is not part of the reference tree, so all of this is PARITY UNPINNED, pinned by tests/ule_ref.py's
  * sequential restatement and its RFC 4326 section 7 receiver.
  *
@@ -699,6 +700,109 @@ int dvbt2ll_ule_run_host(dvbt2ll_ule *h, const void *pdu, int64_t pdu_len, const
                          int64_t n_pdus, const dvbt2ll_ule_pos *start, void *out, int64_t out_cap_packets, int flush,
                          dvbt2ll_ule_result *res);
 void dvbt2ll_ule_destroy(dvbt2ll_ule *h);
+
+/* ---------------------------------------------------------------------------
+ * GSE encapsulator (Generic Stream Encapsulation, ETSI TS 102 606-1; EN 302 755 5.1.7): a device buffer of PDUs (IP
+ * datagrams) and a device offset table -> one PLP's normal-mode BBFRAMEs with TS/GS = 10, in the layout
+ * DVBT2LL_INPUT_BBFRAME reads (kbch / 8 bytes per BBFRAME, back to back): IP reaches IQ with no TS layer.  A handle
+ * of its own beside the chain: it holds scratch, no stream state.  Not built: extension headers, label reuse (LT 11
+ * on complete packets) and per-PDU labels, PDUs above 4090 - L bytes, several PDUs open at once (QoS interleaving),
+ * HEM / ISSY headers, GSE-Lite signalling.  The reference has no GSE code, so all of this is PARITY UNPINNED, pinned
+ * by tests/gse_ref.py's sequential restatement and its receiver.  The rules are this project's
+ * reading of the two standards.  D = (kbch - 80) / 8 is the data field in bytes, L = label_len (6, 3 or 0), LT = 00 /
+ * 01 / 10 for these.
+ *
+ * input      as the ULE handle's: pdu_dev holds pdu_len bytes (below 2^31); off_dev holds n_pdus + 1 uint32_t
+ *            offsets: PDU i is bytes [off[i], off[i + 1]), len of them.  type_dev is optional: n_pdus uint16_t
+ *            Protocol Types.  With type_dev == NULL the type comes from the PDU's first nibble: 4 -> 0x0800, 6 ->
+ *            0x86DD; any other nibble: the PDU is skipped and counted in skipped_type.  A PDU is skipped and counted
+ *            in skipped_len when off[i + 1] <= off[i], or off[i + 1] > pdu_len, or len > 4090 - L (the length is
+ *            judged first).  The bound keeps every packet's 12-bit GSE Length <= 4095, so no PDU needs two packets in
+ *            one frame.  A skipped PDU contributes nothing (it still takes its place in the Frag ID count); every
+ *            rule below speaks of the valid PDUs.  Nothing outside [pdu_dev, pdu_dev + pdu_len) and the two tables is
+ *            read.  Valid PDUs may overlap or repeat; the frames may then be more than the buffer's bytes suggest.
+ * packets    every GSE packet starts with S, E, LT (2 bits) and GSE Length (12 bits) = the bytes that follow:
+ *              complete        S 1, E 1, the handle's LT: Protocol Type (2), Label (L), the PDU: 4 + L + len bytes
+ *              first fragment  S 1, E 0, the handle's LT: Frag ID (1), Total Length (2) = 2 + L + len, Protocol Type,
+ *                              Label, a piece of the PDU: 7 + L + piece bytes
+ *              continuation    S 0, E 0, LT 11: Frag ID, piece: 3 + piece bytes
+ *              end fragment    S 0, E 1, LT 11: Frag ID, piece, CRC-32: 7 + piece bytes
+ *            The CRC-32 (generator 0x04C11DB7, initial value 0xFFFFFFFF, MSB first, no final XOR, big-endian: the CRC
+ *            ULE uses) covers Total Length, Protocol Type, Label and the whole PDU.  The Frag ID of PDU i is
+ *            (start.frag_id + i - start.pdu) mod 256.  Only one PDU is ever open.
+ * placement  sequential over the PDUs; u is the bytes used in the open data field (0 at a frame's start); a packet
+ *            never crosses a BBFRAME; a frame with u = D is closed.  A fresh PDU with free = D - u:
+ *              free >= 4 + L + len: a complete packet;
+ *              else free >= 8 + L: a first fragment with piece = free - 7 - L, which fills the frame;
+ *              else the frame is closed as it is and the PDU is fresh at u = 0 of the next one.
+ *            An open PDU with rem bytes left (always at u = 0):
+ *              rem + 7 <= D: an end fragment with piece = rem;
+ *              else a continuation with piece = min(D - 3, rem - 1), so that the end fragment always carries a PDU
+ *              byte, and the frame is closed: at most 4 of its bytes stay unused.
+ * BBFRAMEs   normal-mode header: MATYPE-1 = TS/GS 10, SIS/MIS, CCM 1, ISSYI 0, NPD 0, EXT 00 (B0 for SIS); MATYPE-2 =
+ *            the ISI (MIS) or 0; UPL 0; DFL = 8 x the bytes of the frame's packets; SYNC 0; SYNCD 0 (a packet always
+ *            starts at byte 0); CRC-8 with MODE = 0: dvbt2ll_chain_bbheader_errors counts none.  The unused rest of
+ *            the data field is zero and counted in pad_bytes.
+ * capacity   a call emits the closed frames that out_cap_blocks allows and returns resume = {pdu, pdu_byte, frag_id},
+ *            the state at the start of the first frame not emitted: the first valid PDU that continues or starts
+ *            there, the number of its bytes already sent (0: it is fresh), its Frag ID.  A frame still open when the
+ *            input ends is emitted only with flush = 1, and only if it fits the capacity (DFL = 8 u; none when u =
+ *            0); then resume = {n_pdus, 0, the Frag ID n_pdus would have}.  Without flush the open frame's PDUs are
+ *            presented again by the next call, which passes resume as start with a PDU list that begins at or before
+ *            that PDU.  A start whose pdu_byte is not in 1 .. len - 1 of a valid PDU is taken as 0.  Chained calls at
+ *            any split, and after any capacity cut, produce the single call's bytes.
+ * counters   pdus_in, complete, fragmented (PDUs), skipped_len, skipped_type cover the PDUs from start.pdu to before
+ *            resume.pdu, so they add up over chained calls (a PDU an earlier call left open counts as fragmented
+ *            where it ends); gse_packets, bbframes and pad_bytes cover the frames emitted; flushed is 1 when the
+ *            flush frame was written.
+ * bounds     nothing outside out_cap_blocks x kbch / 8 bytes of out_dev is written.
+ * scratch    about 22 bytes per PDU of max_pdus, and a position table of 4 D bytes per 256 PDUs.
+ * ------------------------------------------------------------------------- */
+typedef struct dvbt2ll_gse dvbt2ll_gse;
+typedef struct {
+  int kbch;                              /* one of the chain's 14 Kbch, or 3072; 0: taken from framesize / rate.
+                                            58192 (D = 7264, the DVB family's largest; no T2 code has it and the
+                                            chain takes no such frame) is accepted too: the tests pin the tables there */
+  int framesize, rate;                   /* FECFRAME_* / C*: used when kbch == 0 */
+  int sis_mis;                           /* 1: single input stream; 0: multiple, MATYPE-2 = isi (0 .. 255) */
+  int isi;
+  int label_len;                         /* 6, 3 or 0 (broadcast) */
+  uint8_t label[6];                      /* the first label_len bytes are sent */
+  int64_t max_pdu_bytes;                 /* largest pdu_len of a run, 1 .. 2^31 - 1 */
+  int max_pdus;                          /* largest n_pdus of a run, 1 .. 2^24 */
+} dvbt2ll_gse_params;
+typedef struct {
+  int64_t pdu;                           /* a PDU index in [0, n_pdus] */
+  int pdu_byte;                          /* bytes of that PDU already sent */
+  int frag_id;                           /* 0 .. 255: that PDU's Frag ID */
+} dvbt2ll_gse_pos;
+typedef struct {
+  dvbt2ll_gse_pos resume;
+  int64_t pdus_in, complete, fragmented, gse_packets, skipped_len, skipped_type, bbframes, pad_bytes, flushed;
+} dvbt2ll_gse_result;
+/* DVBT2LL_EINVAL: a null pointer, a Kbch that is neither one of the chain's 14 nor 3072 (nor 58192), sis_mis / isi / the maxima
+ * out of range, a label_len other than 0, 3 or 6; DVBT2LL_EDEVICE without a GPU */
+int dvbt2ll_gse_create(const dvbt2ll_gse_params *p, int device, dvbt2ll_gse **out);
+/* fills kbch, sis_mis and isi from the chain's PLP plp; the other fields stay */
+int dvbt2ll_gse_params_from_chain(const dvbt2ll_chain *chain, int plp, dvbt2ll_gse_params *p);
+/* pdu_dev, off_dev, type_dev (or NULL) on the device; start: {0, 0, frag_id} or a previous call's resume position in
+ * this list's PDU indices; out_dev: room for out_cap_blocks BBFRAMEs of kbch / 8 bytes.  Asynchronous on stream (NULL:
+ * the handle's own); no host round trip.  One run of a handle at a time: the next run call on another stream first
+ * waits for the previous one.  DVBT2LL_EINVAL, nothing launched: a null pointer (type_dev may be), pdu_len or n_pdus
+ * negative or above the create-time maxima, a negative capacity, start.pdu outside [0, n_pdus], a negative pdu_byte,
+ * frag_id outside 0 .. 255. */
+int dvbt2ll_gse_run_device(dvbt2ll_gse *h, const void *pdu_dev, int64_t pdu_len, const uint32_t *off_dev,
+                           const uint16_t *type_dev, int64_t n_pdus, const dvbt2ll_gse_pos *start, void *out_dev,
+                           int64_t out_cap_blocks, int flush, void *stream);
+/* synchronises with the last run and returns its result */
+int dvbt2ll_gse_get_result(dvbt2ll_gse *h, dvbt2ll_gse_result *res);
+/* host buffers, synchronous: the PDUs and tables are copied in, the written BBFRAMEs are copied out.  The device
+ * output buffer holds out_cap_blocks, or what n_pdus PDUs inside pdu_len bytes can become at the most if that is
+ * less. */
+int dvbt2ll_gse_run_host(dvbt2ll_gse *h, const void *pdu, int64_t pdu_len, const uint32_t *off, const uint16_t *type,
+                         int64_t n_pdus, const dvbt2ll_gse_pos *start, void *out, int64_t out_cap_blocks, int flush,
+                         dvbt2ll_gse_result *res);
+void dvbt2ll_gse_destroy(dvbt2ll_gse *h);
 
 /* ---------------------------------------------------------------------------
  * ABI version.  The parameter and info structs are passed by pointer with no size field, so a caller
