@@ -35,6 +35,11 @@
 // --label / --label3 / --no-label choose the 6-byte, 3-byte or no label.  The BBFRAMEs then go through the chain's
 // BBFRAME input exactly as a BBFRAME file does.
 //
+// --t2mi-out FILE --t2mi-pid N [--t2mi-stream-id S] writes, next to the IQ, the T2-MI transport stream of exactly the
+// frames encoded (dvbt2ll_t2mi_out_run_host per batch, each batch continuing from the previous one's next position;
+// no auxiliary slots): what a gateway would send to remote modulators, which produce the same IQ from it with
+// --input t2mi.  It needs an input that yields BBFRAMEs: bbframe, ts-npd, gse or t2mi.
+//
 // --mplp runs a multi-PLP frame preset (one TS file per PLP, dvbt2ll_chain_create_mplp / _run_plps_host;
 // batches are whole launch units, dvbt2ll_chain_unit_frames).
 //
@@ -122,6 +127,8 @@ void usage(FILE *f) {
                "  --pid N                 --input t2mi / ule: the PID of the T2-MI stream / of the SNDUs (default 4096)\n"
                "  --plp-id K              --input t2mi: the PLP_ID feeding the next PLP of the preset (repeat per\n"
                "                          PLP; default 0, 1, ...)\n"
+               "  --t2mi-out FILE         also write the T2-MI TS of the frames encoded (--input bbframe, ts-npd, gse, t2mi)\n"
+               "  --t2mi-pid N            its PID (default 4096); --t2mi-stream-id S: its t2mi_stream_id (default 0)\n"
                "  --format cf32|sc16      IQ sample format (default cf32, pilotgen's complex64)\n"
                "  --gain G                output gain (the flowgraph's multiply_const; default 1)\n"
                "  --frames N              T2 frames to encode (default: as many as the input holds)\n"
@@ -176,12 +183,66 @@ struct TsIn {
   }
 };
 
+// --t2mi-out: the gateway's view of the frames encoded.  One framer call per batch; a batch's last TS packet is stuffed.
+struct T2miOut {
+  std::string path;
+  int pid = 4096, stream_id = 0;
+  dvbt2ll_t2mi_out *fr = nullptr;
+  FILE *f = nullptr;
+  dvbt2ll_t2mi_out_pos pos = {0, 0, 0};
+  dvbt2ll_t2mi_out_result tot;
+  std::vector<uint8_t> ts;
+  int open(const dvbt2ll_chain *chain, const std::vector<int> &plp_ids, int batch, int device) {
+    std::memset(&tot, 0, sizeof(tot));
+    dvbt2ll_t2mi_out_params op;
+    std::memset(&op, 0, sizeof(op));
+    if (!plp_ids.empty() && (int)plp_ids.size() != dvbt2ll_chain_num_plps(chain)) return DVBT2LL_EINVAL;
+    int st = dvbt2ll_t2mi_out_params_from_chain(chain, plp_ids.empty() ? nullptr : plp_ids.data(), &op);
+    if (st) {
+      std::fprintf(stderr, "dvbt2ll_tx: --t2mi-out: a PLP's interleaving frame spans several T2 frames or skips frames: not supported\n");
+      return st;
+    }
+    op.pid = pid;
+    op.t2mi_stream_id = stream_id;
+    op.max_frames = batch;
+    if ((st = dvbt2ll_t2mi_out_create(&op, device, &fr))) {
+      std::fprintf(stderr, "dvbt2ll_tx: --t2mi-out: %s\n", dvbt2ll_strerror(st));
+      return st;
+    }
+    ts.resize((size_t)dvbt2ll_t2mi_out_ts_packets(fr, batch) * 188);
+    f = std::fopen(path.c_str(), "wb");
+    if (!f) { std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", path.c_str(), std::strerror(errno)); return -1; }
+    return 0;
+  }
+  // bb[k]: PLP k's BBFRAMEs of the n frames just encoded
+  int write(const void *const *bb, int n) {
+    dvbt2ll_t2mi_out_result res;
+    int st = dvbt2ll_t2mi_out_run_host(fr, bb, nullptr, 0, nullptr, &pos, n, ts.data(), (int64_t)(ts.size() / 188), &res);
+    if (st) { std::fprintf(stderr, "dvbt2ll_tx: --t2mi-out: %s\n", dvbt2ll_strerror(st)); return st; }
+    if (std::fwrite(ts.data(), 188, (size_t)res.ts_packets, f) != (size_t)res.ts_packets) return -1;
+    pos = res.next;
+    int64_t *a = &tot.frames, *b = &res.frames;
+    for (int i = 0; i < 5; i++) a[i] += b[i];
+    return 0;
+  }
+  void close() {
+    if (fr)
+      std::fprintf(stderr, "dvbt2ll_tx: t2mi-out: %lld T2 frames, t2mi_packets %lld, ts_packets %lld, pusi_packets %lld, "
+                   "stuffing_bytes %lld\n", (long long)tot.frames, (long long)tot.t2mi_packets, (long long)tot.ts_packets,
+                   (long long)tot.pusi_packets, (long long)tot.stuffing_bytes);
+    if (f) std::fclose(f);
+    dvbt2ll_t2mi_out_destroy(fr);
+    fr = nullptr;
+    f = nullptr;
+  }
+};
+
 constexpr int kInputT2mi = 2;   // --input t2mi (the chain itself runs in DVBT2LL_INPUT_BBFRAME)
 
 // --input t2mi: the file's TS -> T2-MI deframer in chunks -> per-PLP BBFRAME queues -> whole launch units through
 // dvbt2ll_chain_run_plps_host.  h: a chain of any preset, already in BBFRAME input with its output set.
 int run_t2mi(dvbt2ll_chain *h, const std::string &in_path, const std::string &out_path, int fmt, int pid,
-             const std::vector<int> &plp_ids, int64_t frames, int batch, int device) {
+             const std::vector<int> &plp_ids, int64_t frames, int batch, int device, T2miOut *gw) {
   const int nplp = dvbt2ll_chain_num_plps(h), unit = dvbt2ll_chain_unit_frames(h);
   if (!plp_ids.empty() && (int)plp_ids.size() != nplp) {
     std::fprintf(stderr, "dvbt2ll_tx: --plp-id: give one per PLP (%d)\n", nplp);
@@ -282,6 +343,11 @@ int run_t2mi(dvbt2ll_chain *h, const std::string &in_path, const std::string &ou
       if ((st = dvbt2ll_chain_run_plps_host(h, ptr, base, ql, done, (int)n, iq.data()))) break;
       const size_t bytes = (size_t)n * pi[0].iq_samples_per_frame * sb;
       if (std::fwrite(iq.data(), 1, bytes, fout) != bytes) { st = -1; break; }
+      if (gw) {   // frames_per_if = 1 (T2miOut::open): frame `done` begins ts_bytes_per_frame x done into the stream
+        const void *bb[DVBT2LL_MAX_PLP];
+        for (int k = 0; k < nplp; k++) bb[k] = q[k].data() + (size_t)(done * pi[k].ts_bytes_per_frame - q_base[k]);
+        if ((st = gw->write(bb, (int)n))) break;
+      }
       done += n;
       for (int k = 0; k < nplp; k++) {   // drop the interleaving frames no later T2 frame needs
         const int64_t nb = done / pi[k].frames_per_if * pi[k].ts_bytes_per_frame;
@@ -324,7 +390,7 @@ constexpr int kInputTsNpd = 3;   // --input ts-npd (the chain itself runs in DVB
 // --input ts-npd: the file's TS -> one mode adapter per PLP in chunks -> per-PLP BBFRAME queues -> whole launch units
 // through dvbt2ll_chain_run_plps_host.  h: a chain of any preset, already in BBFRAME input with its output set.
 int run_tsnpd(dvbt2ll_chain *h, const std::string &in_path, const std::string &out_path, int fmt,
-              const std::vector<std::vector<int>> &pids, int64_t frames, int batch, int device) {
+              const std::vector<std::vector<int>> &pids, int64_t frames, int batch, int device, T2miOut *gw) {
   const int nplp = dvbt2ll_chain_num_plps(h), unit = dvbt2ll_chain_unit_frames(h);
   if (!pids.empty() && (int)pids.size() != nplp) {
     std::fprintf(stderr, "dvbt2ll_tx: --pids: give one list per PLP (%d)\n", nplp);
@@ -415,6 +481,11 @@ int run_tsnpd(dvbt2ll_chain *h, const std::string &in_path, const std::string &o
     if ((st = dvbt2ll_chain_run_plps_host(h, ptr, base, ql, done, (int)n, iq.data()))) break;
     const size_t bytes = (size_t)n * pl[0].info.iq_samples_per_frame * sb;
     if (std::fwrite(iq.data(), 1, bytes, fout) != bytes) { st = -1; break; }
+    if (gw) {
+      const void *bb[DVBT2LL_MAX_PLP];
+      for (int k = 0; k < nplp; k++) bb[k] = pl[k].q.data() + (size_t)(done * pl[k].info.ts_bytes_per_frame - pl[k].q_base);
+      if ((st = gw->write(bb, (int)n))) break;
+    }
     done += n;
     for (int k = 0; k < nplp; k++) {   // drop the interleaving frames no later T2 frame needs
       const int64_t nb = done / pl[k].info.frames_per_if * pl[k].info.ts_bytes_per_frame;
@@ -597,7 +668,8 @@ FILE *run_gse(const dvbt2ll_chain *chain, const std::string &in_path, int label_
 // the multi-PLP transmitter: whole launch units per batch, each PLP's TS span from its own file
 int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const std::string &out_path, int fmt,
              float gain, int64_t frames, int batch, int device, bool print_params, int input = DVBT2LL_INPUT_TS,
-             int pid = 0, const std::vector<int> &plp_ids = {}, const std::vector<std::vector<int>> &pids = {}) {
+             int pid = 0, const std::vector<int> &plp_ids = {}, const std::vector<std::vector<int>> &pids = {},
+             T2miOut *gw = nullptr) {
   dvbt2ll_mplp_chain_params p;
   std::memset(&p, 0, sizeof(p));
   dvbt2ll_mplp_params &m = p.fm;
@@ -640,8 +712,11 @@ int run_mplp(const MplpPreset &ps, const std::vector<std::string> &ins, const st
     return 1;
   }
   if (t2mi) {
-    const int rc = tsnpd ? run_tsnpd(h, ins[0], out_path, fmt, pids, frames, batch, device)
-                         : run_t2mi(h, ins[0], out_path, fmt, pid, plp_ids, frames, batch, device);
+    int rc = gw && gw->open(h, plp_ids, batch, device) ? 1 : 0;
+    if (!rc)
+      rc = tsnpd ? run_tsnpd(h, ins[0], out_path, fmt, pids, frames, batch, device, gw)
+                 : run_t2mi(h, ins[0], out_path, fmt, pid, plp_ids, frames, batch, device, gw);
+    if (gw) gw->close();
     dvbt2ll_chain_destroy(h);
     return rc;
   }
@@ -706,6 +781,7 @@ int main(int argc, char **argv) {
   int ule_d_bit = 0, ule_packing = 1;
   uint8_t gse_label[6] = {0x02, 0x00, 0x48, 0x55, 0x4C, 0x4B};
   int gse_label_len = 6;
+  T2miOut gw;
   bool print_params = false;
   int64_t frames = -1;
   float gain = 1.f;
@@ -768,6 +844,9 @@ int main(int argc, char **argv) {
     else if (a == "--no-dest") ule_d_bit = 1;
     else if (a == "--packing") ule_packing = std::atoi(next());
     else if (a == "--plp-id") plp_ids.push_back((int)std::strtol(next(), nullptr, 0));
+    else if (a == "--t2mi-out") gw.path = next();
+    else if (a == "--t2mi-pid") gw.pid = (int)std::strtol(next(), nullptr, 0);
+    else if (a == "--t2mi-stream-id") gw.stream_id = (int)std::strtol(next(), nullptr, 0);
     else if (a == "--gain") gain = std::strtof(next(), nullptr);
     else if (a == "--frames") frames = std::strtoll(next(), nullptr, 10);
     else if (a == "--batch") batch = std::atoi(next());
@@ -776,6 +855,11 @@ int main(int argc, char **argv) {
     else { std::fprintf(stderr, "dvbt2ll_tx: unknown option %s\n", a.c_str()); usage(stderr); return 2; }
   }
 
+  T2miOut *gwp = gw.path.empty() ? nullptr : &gw;
+  if (gwp && !print_params && (input == DVBT2LL_INPUT_TS || input == kInputUle)) {
+    std::fprintf(stderr, "dvbt2ll_tx: --t2mi-out needs an input that yields BBFRAMEs: --input bbframe, ts-npd, gse or t2mi\n");
+    return 2;
+  }
   if (!mplp.empty()) {
     if (input == DVBT2LL_INPUT_BBFRAME || input == kInputUle || input == kInputGse) {
       std::fprintf(stderr, "dvbt2ll_tx: --input bbframe / ule / gse takes a single-PLP preset\n");
@@ -783,7 +867,7 @@ int main(int argc, char **argv) {
     }
     for (auto &q : kMplpPresets)
       if (mplp == q.name)
-        return run_mplp(q, ins, out_path, fmt, gain, frames, batch, device, print_params, input, pid, plp_ids, pids);
+        return run_mplp(q, ins, out_path, fmt, gain, frames, batch, device, print_params, input, pid, plp_ids, pids, gwp);
     std::fprintf(stderr, "dvbt2ll_tx: unknown multi-PLP preset %s\n", mplp.c_str());
     return 2;
   }
@@ -828,9 +912,15 @@ int main(int argc, char **argv) {
     dvbt2ll_chain_destroy(h);
     return 1;
   }
+  if (gwp && gwp->open(h, plp_ids, batch, device)) {
+    gwp->close();
+    dvbt2ll_chain_destroy(h);
+    return 1;
+  }
   if (t2mi) {
-    const int rc = tsnpd ? run_tsnpd(h, in_path, out_path, fmt, pids, frames, batch, device)
-                         : run_t2mi(h, in_path, out_path, fmt, pid, plp_ids, frames, batch, device);
+    const int rc = tsnpd ? run_tsnpd(h, in_path, out_path, fmt, pids, frames, batch, device, gwp)
+                         : run_t2mi(h, in_path, out_path, fmt, pid, plp_ids, frames, batch, device, gwp);
+    if (gwp) gwp->close();
     dvbt2ll_chain_destroy(h);
     return rc;
   }
@@ -838,6 +928,7 @@ int main(int argc, char **argv) {
                   : gse ? run_gse(h, in_path, gse_label_len, gse_label, device)
                   : in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
   if ((ule || gse) && !fin) {
+    if (gwp) gwp->close();
     dvbt2ll_chain_destroy(h);
     return 1;
   }
@@ -924,6 +1015,10 @@ int main(int argc, char **argv) {
     std::memcpy(ts_pin[sl], ts.data() + (lo - ts_base), (size_t)span);
     st = dvbt2ll_chain_host_submit(h, ts_pin[sl], lo, span, done, n, iq_pin[sl], &ticket[sl]);
     if (st) { std::fprintf(stderr, "dvbt2ll_tx: run: %s\n", dvbt2ll_strerror(st)); break; }
+    if (gwp) {   // BBFRAME input: the span is exactly the n frames' BBFRAMEs
+      const void *bb[1] = {ts_pin[sl]};
+      if ((st = gwp->write(bb, n))) break;
+    }
     slot_frames[sl] = n;
     submitted++;
     done += n;
@@ -936,6 +1031,7 @@ int main(int argc, char **argv) {
                dt > 0 ? done * info.iq_samples_per_frame / dt / 1e6 : 0.0);
   if (fin != stdin) std::fclose(fin);
   if (fout != stdout) std::fclose(fout);
+  if (gwp) gwp->close();
   (void)dvbt2ll_chain_synchronize(h);
   for (int k = 0; k < R; k++) {
     if (submitted > written) (void)dvbt2ll_chain_host_wait(h, ticket[k]);   // nothing in flight on the buffers

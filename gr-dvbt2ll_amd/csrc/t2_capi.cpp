@@ -21,6 +21,7 @@
 #include "ule_kernels.h"
 #include "gse_kernels.h"
 #include "t2mi_kernels.h"
+#include "t2mi_out_kernels.h"
 
 using namespace t2;
 
@@ -2464,3 +2465,229 @@ extern "C" int dvbt2ll_gse_run_host(dvbt2ll_gse *h, const void *pdu, int64_t pdu
 }
 
 extern "C" void dvbt2ll_gse_destroy(dvbt2ll_gse *h) { delete h; }
+
+// ============================================================================ T2-MI output
+// A handle beside the chain, built like the T2-MI input one.  Every packet length is a constant of the handle and every
+// call starts on a TS packet boundary, so the positions of a call's packets are walked once at create
+// (t2mo_host_walk) and a call's counters are arithmetic on the host: run_device launches the CRC and emit passes on the
+// caller's stream (t2mi_out_kernels.hip) and keeps the result for get_result.
+struct dvbt2ll_t2mi_out {
+  DeviceCtx ctx;
+  dvbt2ll_t2mi_out_params p{};
+  T2moDev dev;
+  T2moFrames frames;
+  std::vector<T2moPkt> pkt;        // P + 1
+  uint32_t aux_bytes[DVBT2LL_T2MI_OUT_MAX_AUX] = {};
+  dvbt2ll_t2mi_out_result res{};   // the last run's
+  DevBuf scratch, bb_tmp[DVBT2LL_MAX_PLP], aux_tmp, out_tmp;
+  hipEvent_t done = nullptr;       // the last run; a run on another stream waits for it (the scratch is shared)
+  hipStream_t last = nullptr;
+  bool ran = false;
+  ~dvbt2ll_t2mi_out() {
+    if (done) { (void)hipSetDevice(ctx.device); (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+  }
+};
+
+// the packets of one T2 frame, or nothing when the parameters are refused
+static std::vector<T2moPkt> t2mo_frame_packets(const dvbt2ll_t2mi_out_params &p) {
+  std::vector<T2moPkt> out;
+  if (p.pid < 0 || p.pid > 0x1FFE || p.t2mi_stream_id < 0 || p.t2mi_stream_id > 7) return out;
+  if (p.nplp < 1 || p.nplp > DVBT2LL_MAX_PLP || p.naux < 0 || p.naux > DVBT2LL_T2MI_OUT_MAX_AUX) return out;
+  if (p.frames_per_superframe < 1 || p.frames_per_superframe > 256 || p.max_frames < 1) return out;
+  for (int k = 0; k < p.nplp; k++) {
+    if (p.plp_id[k] < 0 || p.plp_id[k] > 255 || !t2mi_valid_len(p.bbframe_bytes[k])) return out;
+    if (p.blocks_per_frame[k] < 1 || p.blocks_per_frame[k] > 1023) return out;
+    for (int j = 0; j < k; j++)
+      if (p.plp_id[j] == p.plp_id[k]) return out;
+  }
+  for (int a = 0; a < p.naux; a++) {
+    const dvbt2ll_t2mi_out_slot &s = p.aux[a];
+    if (s.packet_type < 0 || s.packet_type > 255 || s.payload_bits < 1 || s.payload_bits > 65535) return out;
+    if (s.after != 0 && s.after != 1) return out;
+  }
+  uint64_t off = 0;
+  auto add_aux = [&](int after) {
+    for (int a = 0; a < p.naux; a++) {
+      if (p.aux[a].after != after) continue;
+      const uint32_t bits = (uint32_t)p.aux[a].payload_bits;
+      out.push_back({(uint32_t)off, 10 + (bits + 7) / 8, 0, (uint16_t)bits, (uint8_t)p.aux[a].packet_type, (uint8_t)(8 + a)});
+      off += out.back().T;
+    }
+  };
+  add_aux(0);
+  for (int k = 0; k < p.nplp; k++)
+    for (int b = 0; b < p.blocks_per_frame[k]; b++) {
+      const uint32_t L = (uint32_t)p.bbframe_bytes[k];
+      out.push_back({(uint32_t)off, 13 + L, (uint32_t)b, (uint16_t)(24 + 8 * L), 0, (uint8_t)k});
+      off += out.back().T;
+    }
+  add_aux(1);
+  if (off * (uint64_t)p.max_frames >= ((uint64_t)1 << 31) - ((uint64_t)1 << 24)) return {};
+  out.push_back({(uint32_t)off, 0, 0, 0, 0, 0});   // the frame's end
+  return out;
+}
+
+extern "C" int dvbt2ll_t2mi_out_create(const dvbt2ll_t2mi_out_params *p, int device, dvbt2ll_t2mi_out **out) {
+  if (!p || !out) return DVBT2LL_EINVAL;
+  *out = nullptr;
+  std::vector<T2moPkt> pkt = t2mo_frame_packets(*p);
+  if (pkt.empty()) return DVBT2LL_EINVAL;
+  std::unique_ptr<dvbt2ll_t2mi_out> h(new (std::nothrow) dvbt2ll_t2mi_out());
+  if (!h) return DVBT2LL_ENOMEM;
+  h->p = *p;
+  int r = h->ctx.init(device);
+  if (r) return r;
+  T2moDev &d = h->dev;
+  d.pid = p->pid;
+  d.stream_id = p->t2mi_stream_id;
+  d.nplp = p->nplp;
+  d.fps = p->frames_per_superframe;
+  for (int k = 0; k < p->nplp; k++) {
+    d.plp_id[k] = p->plp_id[k];
+    d.Lb[k] = (uint32_t)p->bbframe_bytes[k];
+    d.F[k] = (uint32_t)p->blocks_per_frame[k];
+  }
+  for (int a = 0; a < p->naux; a++) h->aux_bytes[a] = ((uint32_t)p->aux[a].payload_bits + 7) / 8;
+  d.P = (uint32_t)pkt.size() - 1;
+  d.B = pkt.back().off;
+  d.max_frames = (uint32_t)p->max_frames;
+  std::vector<uint32_t> tq;
+  std::vector<uint8_t> td;
+  t2mo_host_walk(d, pkt.data(), tq, td, h->frames);
+  if (h->scratch.ensure(t2mo_layout(d, nullptr))) return DVBT2LL_ENOMEM;
+  (void)t2mo_layout(d, h->scratch.p);
+  std::vector<uint32_t> tab(T2MO_TAB_WORDS);
+  t2mo_host_tables(tab.data());
+  HIP_TRY(hipMemcpy(d.tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.pkt, pkt.data(), pkt.size() * sizeof(T2moPkt), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.tq, tq.data(), tq.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.td, td.data(), td.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+  h->pkt = std::move(pkt);
+  *out = h.release();
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_t2mi_out_params_from_chain(const dvbt2ll_chain *chain, const int *plp_ids,
+                                                  dvbt2ll_t2mi_out_params *p) {
+  if (!chain || !p || chain->nplp < 1 || chain->nplp > DVBT2LL_MAX_PLP) return DVBT2LL_EINVAL;
+  for (int k = 0; k < chain->nplp; k++)
+    if (chain->plps[k]->cyc != 1 || chain->plps[k]->P != 1) return DVBT2LL_EINVAL;   // P_I x I_JUMP > 1: not built
+  p->nplp = chain->nplp;
+  for (int k = 0; k < chain->nplp; k++) {
+    p->plp_id[k] = plp_ids ? plp_ids[k] : k;
+    p->bbframe_bytes[k] = (int)chain->plps[k]->bbf_len();
+    p->blocks_per_frame[k] = chain->plps[k]->F;
+  }
+  p->frames_per_superframe = std::max(1, chain->frame.t2frames);
+  return DVBT2LL_OK;
+}
+
+extern "C" int64_t dvbt2ll_t2mi_out_ts_packets(const dvbt2ll_t2mi_out *h, int nframes) {
+  if (!h || nframes < 0 || nframes > h->p.max_frames) return DVBT2LL_EINVAL;
+  return (int64_t)h->frames.ts_packets((uint32_t)nframes);
+}
+
+static int t2mo_run_args(const dvbt2ll_t2mi_out *h, const void *const *bb, const void *aux, int64_t aux_stride,
+                         const int64_t *aux_off, const dvbt2ll_t2mi_out_pos *start, int nframes, void *out,
+                         int64_t cap, T2moRun &r) {
+  if (!h || !bb || !start || !out) return DVBT2LL_EINVAL;
+  if (nframes < 0 || nframes > h->p.max_frames) return DVBT2LL_EINVAL;
+  if (start->frame < 0 || start->packet_count < 0 || start->packet_count > 255 || start->cc < 0 || start->cc > 15)
+    return DVBT2LL_EINVAL;
+  for (int k = 0; k < h->p.nplp; k++)
+    if (!bb[k]) return DVBT2LL_EINVAL;
+  if (h->p.naux) {
+    if (!aux || !aux_off || aux_stride < 0) return DVBT2LL_EINVAL;
+    for (int a = 0; a < h->p.naux; a++)
+      if (aux_off[a] < 0 || aux_off[a] > 0x7FFFFFFF) return DVBT2LL_EINVAL;
+  }
+  const uint32_t n = (uint32_t)nframes;
+  r.N = h->frames.ts_packets(n);
+  if (cap < (int64_t)r.N) return DVBT2LL_EINVAL;
+  for (int k = 0; k < h->p.nplp; k++) r.bb[k] = (const uint8_t *)bb[k];
+  r.aux = (const uint8_t *)aux;
+  r.aux_stride = h->p.naux ? (size_t)aux_stride : 0;
+  for (int a = 0; a < h->p.naux; a++) r.aux_off[a] = (uint32_t)aux_off[a];
+  const int64_t fps = h->p.frames_per_superframe;
+  r.fi0 = (uint32_t)(start->frame % fps);
+  r.sf0 = (uint32_t)((start->frame / fps) & 15);
+  r.count0 = (uint32_t)start->packet_count;
+  r.cc0 = (uint32_t)start->cc;
+  r.nframes = n;
+  r.G = n * h->dev.P;
+  r.E = n * h->dev.B;
+  r.out = (uint8_t *)out;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_t2mi_out_run_device(dvbt2ll_t2mi_out *h, const void *const *bb_dev, const void *aux_dev,
+                                           int64_t aux_stride, const int64_t *aux_off,
+                                           const dvbt2ll_t2mi_out_pos *start, int nframes, void *out_dev,
+                                           int64_t out_cap_packets, void *stream) {
+  T2moRun r;
+  int e = t2mo_run_args(h, bb_dev, aux_dev, aux_stride, aux_off, start, nframes, out_dev, out_cap_packets, r);
+  if (e) return e;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->ctx.stream;
+  if (h->ran && h->last != st) HIP_TRY(hipStreamWaitEvent(st, h->done, 0));
+  HIP_TRY(t2mo_launch(h->dev, r, st));
+  HIP_TRY(hipEventRecord(h->done, st));
+  h->last = st;
+  h->ran = true;
+  // the result is arithmetic on the handle's constants
+  dvbt2ll_t2mi_out_result &res = h->res;
+  memset(&res, 0, sizeof res);
+  res.next.frame = start->frame + nframes;
+  res.next.packet_count = (int)((r.count0 + r.G) & 255);
+  res.next.cc = (int)((r.cc0 + r.N) & 15);
+  res.frames = nframes;
+  res.t2mi_packets = r.G;
+  res.ts_packets = r.N;
+  res.pusi_packets = h->frames.pusi[r.nframes];
+  res.stuffing_bytes = (int64_t)r.N * 184 - (int64_t)r.E - res.pusi_packets;
+  for (uint32_t j = 0; j < h->dev.P; j++) res.by_type[h->pkt[j].type] += nframes;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_t2mi_out_get_result(dvbt2ll_t2mi_out *h, dvbt2ll_t2mi_out_result *res) {
+  if (!h || !res) return DVBT2LL_EINVAL;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  *res = h->res;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_t2mi_out_run_host(dvbt2ll_t2mi_out *h, const void *const *bb, const void *aux,
+                                         int64_t aux_stride, const int64_t *aux_off, const dvbt2ll_t2mi_out_pos *start,
+                                         int nframes, void *out, int64_t out_cap_packets, dvbt2ll_t2mi_out_result *res) {
+  T2moRun r;
+  if (!res) return DVBT2LL_EINVAL;
+  int e = t2mo_run_args(h, bb, aux, aux_stride, aux_off, start, nframes, out, out_cap_packets, r);
+  if (e) return e;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  hipStream_t st = h->ctx.stream;
+  const void *bd[DVBT2LL_MAX_PLP] = {};
+  for (int k = 0; k < h->p.nplp; k++) {
+    const size_t bytes = (size_t)nframes * h->dev.F[k] * h->dev.Lb[k];
+    if (h->bb_tmp[k].ensure(std::max<size_t>(bytes, 1))) return DVBT2LL_ENOMEM;
+    if (bytes) HIP_TRY(hipMemcpyAsync(h->bb_tmp[k].p, bb[k], bytes, hipMemcpyHostToDevice, st));
+    bd[k] = h->bb_tmp[k].p;
+  }
+  size_t aux_len = 0;   // up to the end of the last frame's last payload
+  if (nframes)
+    for (int a = 0; a < h->p.naux; a++)
+      aux_len = std::max(aux_len, (size_t)(nframes - 1) * r.aux_stride + r.aux_off[a] + h->aux_bytes[a]);
+  if (h->aux_tmp.ensure(std::max<size_t>(aux_len, 1))) return DVBT2LL_ENOMEM;
+  if (aux_len) HIP_TRY(hipMemcpyAsync(h->aux_tmp.p, aux, aux_len, hipMemcpyHostToDevice, st));
+  if (h->out_tmp.ensure(std::max<size_t>((size_t)r.N * 188, 1))) return DVBT2LL_ENOMEM;
+  if ((e = dvbt2ll_t2mi_out_run_device(h, bd, h->aux_tmp.p, aux_stride, aux_off, start, nframes, h->out_tmp.p, r.N,
+                                       st)))
+    return e;
+  if ((e = dvbt2ll_t2mi_out_get_result(h, res))) return e;
+  if (r.N) HIP_TRY(hipMemcpy(out, h->out_tmp.p, (size_t)r.N * 188, hipMemcpyDeviceToHost));
+  return DVBT2LL_OK;
+}
+
+extern "C" void dvbt2ll_t2mi_out_destroy(dvbt2ll_t2mi_out *h) { delete h; }

@@ -10,6 +10,7 @@ from .blocks import bbheaderbch_bb, ldpc_bb, interleavermod_bc, framemapperfint_
 from .blocks import framemapper_mplp_cc  # noqa: F401
 from .chain import Chain, IQ_CF32, IQ_SC16, INPUT_TS, INPUT_BBFRAME  # noqa: F401
 from .t2mi import T2miDeframer, T2miResult  # noqa: F401
+from .t2mi_out import T2miFramer, T2miOutPos, T2miOutResult, AuxSlot  # noqa: F401
 from .modeadapt import ModeAdapter, ModeAdaptPos, ModeAdaptResult  # noqa: F401
 from .ule import UleEncapsulator, UlePos, UleResult  # noqa: F401
 from .gse import GseEncapsulator, GsePos, GseResult  # noqa: F401

@@ -150,6 +150,30 @@ class _GseResult(ctypes.Structure):
         "flushed")]
 
 
+T2MI_OUT_MAX_AUX = 4   # DVBT2LL_T2MI_OUT_MAX_AUX
+
+
+class _T2miOutSlot(ctypes.Structure):
+    _fields_ = [("packet_type", ctypes.c_int), ("payload_bits", ctypes.c_int), ("after", ctypes.c_int)]
+
+
+class _T2miOutParams(ctypes.Structure):
+    _fields_ = [("pid", ctypes.c_int), ("t2mi_stream_id", ctypes.c_int), ("nplp", ctypes.c_int),
+                ("plp_id", ctypes.c_int * MAX_PLP), ("bbframe_bytes", ctypes.c_int * MAX_PLP),
+                ("blocks_per_frame", ctypes.c_int * MAX_PLP), ("frames_per_superframe", ctypes.c_int),
+                ("naux", ctypes.c_int), ("aux", _T2miOutSlot * T2MI_OUT_MAX_AUX), ("max_frames", ctypes.c_int)]
+
+
+class _T2miOutPos(ctypes.Structure):
+    _fields_ = [("frame", ctypes.c_int64), ("packet_count", ctypes.c_int), ("cc", ctypes.c_int)]
+
+
+class _T2miOutResult(ctypes.Structure):
+    _fields_ = [("next", _T2miOutPos)] + [(n, ctypes.c_int64) for n in (
+        "frames", "t2mi_packets", "ts_packets", "pusi_packets", "stuffing_bytes")] + [
+        ("by_type", ctypes.c_int64 * 256)]
+
+
 BLOCKS = ("bbheaderbch", "ldpc", "interleavermod", "framemapperfint", "pilotgenp1insert")
 PARAMS = {"bbheaderbch": _BbParams, "ldpc": _LdpcParams, "interleavermod": _ImParams,
           "framemapperfint": _FmParams, "pilotgenp1insert": _PgParams}
@@ -166,6 +190,8 @@ EXPORTS += ["dvbt2ll_framemapper_mplp_" + f for f in ("create", "output_multiple
                                                       "general_work", "destroy")]
 EXPORTS += ["dvbt2ll_gse_" + f for f in ("create", "params_from_chain", "run_device", "get_result", "run_host",
                                          "destroy")]
+EXPORTS += ["dvbt2ll_t2mi_out_" + f for f in ("create", "params_from_chain", "ts_packets", "run_device", "get_result",
+                                              "run_host", "destroy")]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("host_submit", "host_wait", "run_host_pipelined", "run_plps_host")]
 EXPORTS += ["dvbt2ll_host_alloc", "dvbt2ll_host_free"]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create_mplp", "num_plps", "unit_frames", "get_plp_info", "run_plps",
@@ -299,6 +325,17 @@ def lib():
                                        ctypes.POINTER(_GseResult)]
     L.dvbt2ll_gse_destroy.argtypes = [vp]
     L.dvbt2ll_gse_destroy.restype = None
+    L.dvbt2ll_t2mi_out_create.argtypes = [ctypes.POINTER(_T2miOutParams), ci, ctypes.POINTER(vp)]
+    L.dvbt2ll_t2mi_out_params_from_chain.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(_T2miOutParams)]
+    L.dvbt2ll_t2mi_out_ts_packets.argtypes = [vp, ci]
+    L.dvbt2ll_t2mi_out_ts_packets.restype = i64
+    L.dvbt2ll_t2mi_out_run_device.argtypes = [vp, ctypes.POINTER(vp), vp, i64, ctypes.POINTER(i64),
+                                              ctypes.POINTER(_T2miOutPos), ci, vp, i64, vp]
+    L.dvbt2ll_t2mi_out_get_result.argtypes = [vp, ctypes.POINTER(_T2miOutResult)]
+    L.dvbt2ll_t2mi_out_run_host.argtypes = [vp, ctypes.POINTER(vp), vp, i64, ctypes.POINTER(i64),
+                                            ctypes.POINTER(_T2miOutPos), ci, vp, i64, ctypes.POINTER(_T2miOutResult)]
+    L.dvbt2ll_t2mi_out_destroy.argtypes = [vp]
+    L.dvbt2ll_t2mi_out_destroy.restype = None
     L.dvbt2ll_chain_destroy.argtypes = [vp]
     L.dvbt2ll_chain_destroy.restype = None
     _lib = L

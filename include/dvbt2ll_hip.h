@@ -805,6 +805,120 @@ int dvbt2ll_gse_run_host(dvbt2ll_gse *h, const void *pdu, int64_t pdu_len, const
 void dvbt2ll_gse_destroy(dvbt2ll_gse *h);
 
 /* ---------------------------------------------------------------------------
+ * T2-MI output (ETSI TS 102 773 over DVB data piping): per-PLP packed BBFRAMEs on the device -> the 188-byte TS
+ * packets a T2 gateway distributes to its modulators: the inverse of dvbt2ll_t2mi_* above.  A handle of its own beside
+ * the chain: it holds tables and scratch sized at create, no stream state.  The BBFRAMEs are in the layout
+ * DVBT2LL_INPUT_BBFRAME reads and the mode adapter, the GSE encapsulator and the T2-MI deframer write, so one GPU can
+ * adapt or encapsulate, ship the result as T2-MI and encode the same buffers to IQ.  The reference has no T2-MI code:
+ * PARITY UNPINNED, pinned by tests/t2mi_out_ref.py (a sequential framer composed from tests/t2mi_ref.py's t2mi_packet
+ * and ts_mux), by t2mi_ref.parse as an independent receiver and by the deframer on the device.
+ * Not built: PLPs whose interleaving frame spans several T2 frames or that skip frames (P_I x I_JUMP > 1;
+ * params_from_chain refuses such a chain); a PLP_NUM_BLOCKS that varies from frame to frame; authoring L1-current or
+ * timestamp payloads from the chain's configuration (they are carried as opaque slots); raw T2-MI without a TS layer;
+ * a PCR or other adaptation-field content; carrying a partial TS packet across calls; FEF, auxiliary-stream I/Q and
+ * addressing packets beyond what an opaque slot carries.
+ *
+ * input      per PLP k a device pointer to packed BBFRAMEs of bbframe_bytes[k] = kbch / 8 bytes, back to back,
+ *            blocks_per_frame[k] = F_k of them per T2 frame: frame f of the call (0 .. nframes - 1) reads blocks
+ *            [f F_k, (f + 1) F_k).  Up to 4 auxiliary packet slots per T2 frame, fixed at create: {packet_type,
+ *            payload_bits, after}.  The payload of slot a in frame f of the call is ceil(payload_bits / 8) bytes at
+ *            aux_dev + f aux_stride + aux_off[a]; it is copied as given, except that the pad bits of the last byte
+ *            (its 8 ceil(payload_bits / 8) - payload_bits low bits) are forced to zero.  This is how a caller carries
+ *            timestamp (0x20) and L1-current (0x10) packets: the handle neither interprets nor authors them.
+ * a call     frames nframes whole T2 frames, numbered start.frame, start.frame + 1, ...
+ * frame      the packets of one T2 frame in order: the slots with after = 0 in slot order; PLP 0's F_0 BBFRAME
+ *            packets, then PLP 1's, and so on; the slots with after = 1 in slot order.
+ * packets    as dvbt2ll_t2mi_* reads them: 6 header bytes (packet_type 8, packet_count 8, superframe_idx 4, rfu 9 = 0,
+ *            t2mi_stream_id 3, payload_len 16 in bits), ceil(payload_len / 8) payload bytes, CRC-32/MPEG-2 (generator
+ *            0x04C11DB7, initial value 0xFFFFFFFF, MSB first, no final XOR) of all bytes before it, big-endian.
+ *            packet_count = (start.packet_count + the packet's index in the call) mod 256; superframe_idx =
+ *            (frame / frames_per_superframe) & 15; t2mi_stream_id from the parameters.  Type 0x00 (a BBFRAME):
+ *            payload_len = 24 + kbch; payload = frame_idx = frame % frames_per_superframe, plp_id[k],
+ *            intl_frame_start in bit 7 of the third byte (rfu 7 = 0), the BBFRAME.  intl_frame_start = 1 on the first
+ *            BBFRAME of each PLP in each T2 frame.
+ * TS layer   the call's packets, concatenated, are its T2-MI byte stream; the output is byte for byte
+ *            tests/t2mi_ref.py ts_mux(packets, pid, cc0 = start.cc).  Every TS packet: sync 47, TEI 0, PUSI, priority
+ *            0, pid, scrambling 00, AFC, continuity counter = (start.cc + its index in the call) mod 16.  A TS packet
+ *            that begins at stream position pos, with s the first packet start at or after pos:
+ *              s - pos in 0 .. 182: PUSI 1, pointer_field = s - pos, then 183 stream bytes;
+ *              s - pos = 183:       PUSI 0, 183 stream bytes (shortened, so that the next TS packet begins on s);
+ *              otherwise:           PUSI 0, 184 stream bytes.
+ *            The call's last TS packet carries what is left.  A body (pointer_field and stream bytes) shorter than 184
+ *            bytes is preceded by an adaptation field of stuff = 184 - body bytes: AFC 11, the length byte a = stuff -
+ *            1, and when a > 0 a flags byte 00 and a - 1 bytes FF; a full body has AFC 01.  Every call starts on a TS
+ *            packet boundary with pointer_field 0 and ends with a stuffed packet (or, when the stream ends on a
+ *            packet's last byte, a full one): a partial TS packet is not carried from call to call, which costs fewer
+ *            than 184 bytes per call and keeps the handle without state.
+ * result     next = {start.frame + nframes, the next packet_count, the next continuity counter}: passed as the next
+ *            call's start, the concatenated outputs are one stream a receiver reads without a discontinuity.
+ *            Counters: frames; t2mi_packets and by_type[packet_type]; ts_packets; pusi_packets; stuffing_bytes (the
+ *            adaptation-field bytes, length bytes included).
+ * capacity   every packet length is a constant of the handle, so the TS packets a call of nframes frames writes are
+ *            known before it is launched: dvbt2ll_t2mi_out_ts_packets.  A call whose out_cap_packets is smaller is
+ *            refused with DVBT2LL_EINVAL and launches nothing.
+ * bounds     nothing but the BBFRAMEs and auxiliary payloads stated above is read; nothing outside the first
+ *            dvbt2ll_t2mi_out_ts_packets(h, nframes) x 188 bytes of out_dev is written.  Source and destination
+ *            pointers of any alignment are accepted.
+ * scratch    9 bytes per T2-MI packet of max_frames frames.
+ * ------------------------------------------------------------------------- */
+#define DVBT2LL_T2MI_OUT_MAX_AUX 4
+typedef struct dvbt2ll_t2mi_out dvbt2ll_t2mi_out;
+typedef struct {
+  int packet_type;                       /* 0 .. 255 */
+  int payload_bits;                      /* 1 .. 65535 */
+  int after;                             /* 0: before the frame's BBFRAME packets; 1: after them */
+} dvbt2ll_t2mi_out_slot;
+typedef struct {
+  int pid;                               /* 0 .. 0x1FFE */
+  int t2mi_stream_id;                    /* 0 .. 7 */
+  int nplp;                              /* 1 .. DVBT2LL_MAX_PLP */
+  int plp_id[DVBT2LL_MAX_PLP];           /* 0 .. 255, distinct */
+  int bbframe_bytes[DVBT2LL_MAX_PLP];    /* kbch / 8 of one of the standard's 14 codes */
+  int blocks_per_frame[DVBT2LL_MAX_PLP]; /* F_k: 1 .. 1023 BBFRAMEs per T2 frame */
+  int frames_per_superframe;             /* 1 .. 256 (frame_idx has 8 bits) */
+  int naux;                              /* 0 .. DVBT2LL_T2MI_OUT_MAX_AUX */
+  dvbt2ll_t2mi_out_slot aux[DVBT2LL_T2MI_OUT_MAX_AUX];
+  int max_frames;                        /* the most T2 frames of a call, >= 1; max_frames frames must stay below
+                                            2^31 - 2^24 stream bytes */
+} dvbt2ll_t2mi_out_params;
+typedef struct {
+  int64_t frame;                         /* >= 0: the T2 frame number of the call's first frame */
+  int packet_count;                      /* 0 .. 255: the first packet's packet_count */
+  int cc;                                /* 0 .. 15: the first TS packet's continuity counter */
+} dvbt2ll_t2mi_out_pos;
+typedef struct {
+  dvbt2ll_t2mi_out_pos next;
+  int64_t frames, t2mi_packets, ts_packets, pusi_packets, stuffing_bytes;
+  int64_t by_type[256];                  /* T2-MI packets per packet_type */
+} dvbt2ll_t2mi_out_result;
+/* DVBT2LL_EINVAL: a null pointer, a field outside the range stated above, more than 4 slots; DVBT2LL_EDEVICE without
+ * a GPU */
+int dvbt2ll_t2mi_out_create(const dvbt2ll_t2mi_out_params *p, int device, dvbt2ll_t2mi_out **out);
+/* fills nplp, plp_id[k] = plp_ids[k] (NULL: k), bbframe_bytes[k], blocks_per_frame[k] and frames_per_superframe
+ * (the chain's t2frames) from a chain; the other fields stay.  DVBT2LL_EINVAL for a chain with a PLP whose
+ * interleaving frame spans more than one T2 frame or that skips frames */
+int dvbt2ll_t2mi_out_params_from_chain(const dvbt2ll_chain *chain, const int *plp_ids, dvbt2ll_t2mi_out_params *p);
+/* the TS packets a call of nframes frames writes (0 .. max_frames), or a negative status */
+int64_t dvbt2ll_t2mi_out_ts_packets(const dvbt2ll_t2mi_out *h, int nframes);
+/* bb_dev[k]: PLP k's nframes x F_k BBFRAMEs on the device; aux_dev (NULL with naux = 0), aux_stride >= 0 and
+ * aux_off[a] >= 0 (NULL with naux = 0): the auxiliary payloads; out_dev: room for out_cap_packets x 188 bytes.
+ * Asynchronous on stream (NULL: the handle's own); no host round trip.  One run of a handle at a time: the next run
+ * call on another stream first waits for the previous one.  DVBT2LL_EINVAL, nothing launched: a null pointer, nframes
+ * outside 0 .. max_frames, start.frame < 0, packet_count outside 0 .. 255, cc outside 0 .. 15, a negative stride or
+ * offset, out_cap_packets below dvbt2ll_t2mi_out_ts_packets(h, nframes). */
+int dvbt2ll_t2mi_out_run_device(dvbt2ll_t2mi_out *h, const void *const *bb_dev, const void *aux_dev,
+                                int64_t aux_stride, const int64_t *aux_off, const dvbt2ll_t2mi_out_pos *start,
+                                int nframes, void *out_dev, int64_t out_cap_packets, void *stream);
+/* synchronises with the last run and returns its result */
+int dvbt2ll_t2mi_out_get_result(dvbt2ll_t2mi_out *h, dvbt2ll_t2mi_out_result *res);
+/* host buffers, synchronous: the BBFRAMEs and the auxiliary bytes from aux up to the end of the last frame's last
+ * payload are copied in, the written packets are copied out */
+int dvbt2ll_t2mi_out_run_host(dvbt2ll_t2mi_out *h, const void *const *bb, const void *aux, int64_t aux_stride,
+                              const int64_t *aux_off, const dvbt2ll_t2mi_out_pos *start, int nframes, void *out,
+                              int64_t out_cap_packets, dvbt2ll_t2mi_out_result *res);
+void dvbt2ll_t2mi_out_destroy(dvbt2ll_t2mi_out *h);
+
+/* ---------------------------------------------------------------------------
  * ABI version.  The parameter and info structs are passed by pointer with no size field, so a caller
  * compiled against another layout would be read or written past its struct.  Version history:
  *   1  rounds 1-4: dvbt2ll_plp_params = the first nine ints, no num_subslices, no frames_per_if;
