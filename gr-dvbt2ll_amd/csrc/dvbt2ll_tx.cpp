@@ -30,6 +30,12 @@
 // destination address (default 02:00:48:55:4c:4b), --no-dest sends none (D = 1), --packing 0 starts a packet per
 // SNDU.  The TS then goes through the chain's TS input exactly as a TS file does.
 //
+// --input mpe reads the same records and wraps them on the GPU in DSM-CC datagram_sections packed into TS packets of
+// --pid (Multi-Protocol Encapsulation, EN 301 192 clause 7; dvbt2ll_mpe_run_host in chunks, continued from each call's
+// resume position, flushed at the end of the file).  --mac sets the MAC address, --mac-from-dest gives datagrams to a
+// multicast group the group's MAC, --packing 0 starts a packet per section.  The TS then goes through the chain's TS
+// input exactly as a TS file does.
+//
 // --input gse reads the same records and wraps them on the GPU in GSE packets laid into normal-mode BBFRAMEs (TS 102
 // 606-1; dvbt2ll_gse_run_host in chunks, continued from each call's resume position, flushed at the end of the file).
 // --label / --label3 / --no-label choose the 6-byte, 3-byte or no label.  The BBFRAMEs then go through the chain's
@@ -109,22 +115,25 @@ void usage(FILE *f) {
                "                          inputmode reservedbiasbits l1scrambled inband; pilotgen:\n"
                "                          misogroup equalization bandwidth; bbheaderbch: tsrate)\n"
                "                          misogroup: 0 TX1, 1 TX2 (pilots only), 2 TX2 with MISO processing\n"
-               "  --input ts|bbframe|t2mi|ts-npd|ule|gse what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
+               "  --input ts|bbframe|t2mi|ts-npd|ule|mpe|gse what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
                "                          of kbch / 8 bytes each (single-PLP presets), or a TS carrying T2-MI\n"
                "                          (one file; single-PLP and --mplp presets)\n"
                "                          ts-npd: a TS adapted on the GPU to HEM BBFRAMEs with null-packet deletion\n"
                "                          ule: records of a 16-bit big-endian length and an IP datagram, wrapped on\n"
                "                          the GPU in ULE SNDUs (RFC 4326) on --pid (single-PLP presets)\n"
+               "                          mpe: the same records, wrapped on the GPU in MPE datagram_sections (EN 301 192)\n"
+               "                          on --pid (single-PLP presets)\n"
                "                          gse: the same records, wrapped on the GPU in GSE packets (TS 102 606-1) in\n"
                "                          normal-mode BBFRAMEs (single-PLP presets)\n"
                "  --label aa:bb:cc:dd:ee:ff | --label3 aa:bb:cc | --no-label\n"
                "                          --input gse: the 6-byte label (default 02:00:48:55:4c:4b), a 3-byte one, none\n"
-               "  --mac aa:bb:cc:dd:ee:ff --input ule: the destination address (default 02:00:48:55:4c:4b)\n"
+               "  --mac aa:bb:cc:dd:ee:ff --input ule / mpe: the destination / MAC address (default 02:00:48:55:4c:4b)\n"
+               "  --mac-from-dest         --input mpe: a datagram to a multicast group carries the group's MAC\n"
                "  --no-dest               --input ule: SNDUs without a destination address (D = 1)\n"
-               "  --packing 0|1           --input ule: pack SNDUs back to back (default 1) or one per packet start\n"
+               "  --packing 0|1           --input ule / mpe: pack SNDUs / sections back to back (default 1) or one per packet start\n"
                "  --pids A,B,...          --input ts-npd: the PIDs of the next PLP of the preset (repeat per PLP;\n"
                "                          default: every PID but 0x1FFF)\n"
-               "  --pid N                 --input t2mi / ule: the PID of the T2-MI stream / of the SNDUs (default 4096)\n"
+               "  --pid N                 --input t2mi / ule / mpe: the PID of the T2-MI stream / SNDUs / sections (default 4096)\n"
                "  --plp-id K              --input t2mi: the PLP_ID feeding the next PLP of the preset (repeat per\n"
                "                          PLP; default 0, 1, ...)\n"
                "  --t2mi-out FILE         also write the T2-MI TS of the frames encoded (--input bbframe, ts-npd, gse, t2mi)\n"
@@ -587,6 +596,85 @@ FILE *run_ule(const std::string &in_path, int pid, int d_bit, const uint8_t *des
   return ts;
 }
 
+constexpr int kInputMpe = 6;   // --input mpe (the chain itself runs in DVBT2LL_INPUT_TS)
+
+// --input mpe: the file's length-prefixed PDUs -> the MPE encapsulator in chunks -> a temporary TS file, which the
+// caller reads as it reads a TS file.  Returns the file rewound, or nullptr.
+FILE *run_mpe(const std::string &in_path, int pid, const uint8_t *mac, int mac_mode, int packing, int device) {
+  const size_t chunk = 4 << 20, max_pdus = 65536;   // PDU bytes and PDUs per encapsulator call
+  dvbt2ll_mpe_params up;
+  std::memset(&up, 0, sizeof(up));
+  up.pid = pid;
+  std::memcpy(up.mac, mac, 6);
+  up.mac_mode = mac_mode;
+  up.packing = packing;
+  up.max_pdu_bytes = (int64_t)chunk + 65536;
+  up.max_pdus = (int)max_pdus;
+  dvbt2ll_mpe *enc = nullptr;
+  int st = dvbt2ll_mpe_create(&up, device, &enc);
+  if (st) { std::fprintf(stderr, "dvbt2ll_tx: mpe: %s\n", dvbt2ll_strerror(st)); return nullptr; }
+  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
+  FILE *ts = std::tmpfile();
+  if (!fin || !ts) {
+    std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : "a temporary file", std::strerror(errno));
+    dvbt2ll_mpe_destroy(enc);
+    return nullptr;
+  }
+  std::vector<uint8_t> pdus, out;
+  std::vector<uint32_t> off(1, 0);
+  dvbt2ll_mpe_pos pos = {0, 0, 0};
+  dvbt2ll_mpe_result tot;
+  std::memset(&tot, 0, sizeof(tot));
+  bool eof = false;
+  while (!st) {
+    while (!eof && pdus.size() < chunk && off.size() <= max_pdus) {
+      uint8_t lb[2];
+      if (std::fread(lb, 1, 2, fin) != 2) { eof = true; break; }
+      const size_t len = ((size_t)lb[0] << 8) | lb[1], old = pdus.size();
+      pdus.resize(old + len);
+      if (len && std::fread(pdus.data() + old, 1, len, fin) != len) { pdus.resize(old); eof = true; break; }   // a cut record
+      off.push_back((uint32_t)pdus.size());
+    }
+    const int64_t n = (int64_t)off.size() - 1;
+    // the records lie side by side in pdus, so this many packets hold them all
+    const int64_t cap = packing ? ((int64_t)pdus.size() + 16 * n) / 183 + 2 : ((int64_t)pdus.size() + 16 * n) / 184 + n + 1;
+    out.resize((size_t)cap * 188);
+    const uint8_t none = 0;
+    dvbt2ll_mpe_result res;
+    if ((st = dvbt2ll_mpe_run_host(enc, pdus.empty() ? &none : pdus.data(), (int64_t)pdus.size(), off.data(), n,
+                                   &pos, out.data(), cap, eof, &res)))
+      break;
+    int64_t *a = &tot.pdus_in, *b = &res.pdus_in;
+    for (int i = 0; i < 9; i++) a[i] += b[i];
+    if (res.ts_packets && std::fwrite(out.data(), 188, (size_t)res.ts_packets, ts) != (size_t)res.ts_packets) { st = -1; break; }
+    // continue from the resume position: drop the PDUs before it
+    const uint32_t cut = off[(size_t)res.resume.pdu];
+    pdus.erase(pdus.begin(), pdus.begin() + cut);
+    off.erase(off.begin(), off.begin() + (size_t)res.resume.pdu);
+    for (uint32_t &o : off) o -= cut;
+    pos = {0, res.resume.section_byte, res.resume.cc};
+    if (eof) break;
+    // nothing consumed and no room to read on (a short datagram with max_pdus skipped records behind it holds its
+    // open packet back for ever): give up, not loop
+    if (res.resume.pdu == 0 && res.ts_packets == 0 && (pdus.size() >= chunk || off.size() > max_pdus)) {
+      std::fprintf(stderr, "dvbt2ll_tx: mpe: no packet completes within %zu bytes / %zu records\n", pdus.size(), off.size() - 1);
+      st = -1;
+      break;
+    }
+  }
+  if (st) std::fprintf(stderr, "dvbt2ll_tx: mpe run failed: %s\n", dvbt2ll_strerror(st));
+  std::fprintf(stderr, "dvbt2ll_tx: mpe: pdus_in %lld, sections %lld, skipped_len %lld, skipped_type %lld, mapped_macs %lld, "
+               "ts_packets %lld, pusi_packets %lld, pad_bytes %lld, flushed %lld\n", (long long)tot.pdus_in,
+               (long long)tot.sections, (long long)tot.skipped_len, (long long)tot.skipped_type,
+               (long long)tot.mapped_macs, (long long)tot.ts_packets, (long long)tot.pusi_packets,
+               (long long)tot.pad_bytes, (long long)tot.flushed);
+  if (fin != stdin) std::fclose(fin);
+  dvbt2ll_mpe_destroy(enc);
+  if (st) { std::fclose(ts); return nullptr; }
+  std::rewind(ts);
+  return ts;
+}
+
 constexpr int kInputGse = 5;   // --input gse (the chain itself runs in DVBT2LL_INPUT_BBFRAME)
 
 // --input gse: the file's length-prefixed PDUs -> the GSE encapsulator in chunks -> a temporary file of BBFRAMEs, which
@@ -778,7 +866,7 @@ int main(int argc, char **argv) {
   std::vector<int> plp_ids;
   std::vector<std::vector<int>> pids;
   uint8_t mac[6] = {0x02, 0x00, 0x48, 0x55, 0x4C, 0x4B};   // the flowgraph's ule_source
-  int ule_d_bit = 0, ule_packing = 1;
+  int ule_d_bit = 0, ule_packing = 1, mpe_mac_mode = 0;
   uint8_t gse_label[6] = {0x02, 0x00, 0x48, 0x55, 0x4C, 0x4B};
   int gse_label_len = 6;
   T2miOut gw;
@@ -812,6 +900,7 @@ int main(int argc, char **argv) {
       else if (v == "t2mi") input = kInputT2mi;
       else if (v == "ts-npd") input = kInputTsNpd;
       else if (v == "ule") input = kInputUle;
+      else if (v == "mpe") input = kInputMpe;
       else if (v == "gse") input = kInputGse;
       else { std::fprintf(stderr, "dvbt2ll_tx: unknown input %s\n", v.c_str()); return 2; }
     } else if (a == "--pid") pid = (int)std::strtol(next(), nullptr, 0);
@@ -842,6 +931,7 @@ int main(int argc, char **argv) {
       gse_label_len = want;
     } else if (a == "--no-label") gse_label_len = 0;
     else if (a == "--no-dest") ule_d_bit = 1;
+    else if (a == "--mac-from-dest") mpe_mac_mode = 1;
     else if (a == "--packing") ule_packing = std::atoi(next());
     else if (a == "--plp-id") plp_ids.push_back((int)std::strtol(next(), nullptr, 0));
     else if (a == "--t2mi-out") gw.path = next();
@@ -856,13 +946,13 @@ int main(int argc, char **argv) {
   }
 
   T2miOut *gwp = gw.path.empty() ? nullptr : &gw;
-  if (gwp && !print_params && (input == DVBT2LL_INPUT_TS || input == kInputUle)) {
+  if (gwp && !print_params && (input == DVBT2LL_INPUT_TS || input == kInputUle || input == kInputMpe)) {
     std::fprintf(stderr, "dvbt2ll_tx: --t2mi-out needs an input that yields BBFRAMEs: --input bbframe, ts-npd, gse or t2mi\n");
     return 2;
   }
   if (!mplp.empty()) {
-    if (input == DVBT2LL_INPUT_BBFRAME || input == kInputUle || input == kInputGse) {
-      std::fprintf(stderr, "dvbt2ll_tx: --input bbframe / ule / gse takes a single-PLP preset\n");
+    if (input == DVBT2LL_INPUT_BBFRAME || input == kInputUle || input == kInputMpe || input == kInputGse) {
+      std::fprintf(stderr, "dvbt2ll_tx: --input bbframe / ule / mpe / gse takes a single-PLP preset\n");
       return 2;
     }
     for (auto &q : kMplpPresets)
@@ -902,9 +992,9 @@ int main(int argc, char **argv) {
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: chain create: %s\n", dvbt2ll_strerror(st)); return 1; }
   dvbt2ll_chain_info info;
   // (the info after set_input: it then counts whole BBFRAMEs)
-  const bool tsnpd = input == kInputTsNpd, ule = input == kInputUle, gse = input == kInputGse;
+  const bool tsnpd = input == kInputTsNpd, ule = input == kInputUle, mpe = input == kInputMpe, gse = input == kInputGse;
   const bool t2mi = input == kInputT2mi || tsnpd;
-  if (ule) input = DVBT2LL_INPUT_TS;   // the encapsulator's TS is read as a TS file is
+  if (ule || mpe) input = DVBT2LL_INPUT_TS;   // the encapsulator's TS is read as a TS file is
   if (gse) input = DVBT2LL_INPUT_BBFRAME;   // the encapsulator's BBFRAMEs are read as a BBFRAME file is
   if ((st = dvbt2ll_chain_set_input(h, -1, t2mi ? DVBT2LL_INPUT_BBFRAME : input)) || (st = dvbt2ll_chain_get_info(h, &info)) ||
       (st = dvbt2ll_chain_set_output(h, gain, fmt))) {
@@ -925,9 +1015,10 @@ int main(int argc, char **argv) {
     return rc;
   }
   FILE *fin = ule ? run_ule(in_path, pid, ule_d_bit, mac, ule_packing, device)
+                  : mpe ? run_mpe(in_path, pid, mac, mpe_mac_mode, ule_packing, device)
                   : gse ? run_gse(h, in_path, gse_label_len, gse_label, device)
                   : in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
-  if ((ule || gse) && !fin) {
+  if ((ule || mpe || gse) && !fin) {
     if (gwp) gwp->close();
     dvbt2ll_chain_destroy(h);
     return 1;

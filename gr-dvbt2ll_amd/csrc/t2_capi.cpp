@@ -19,6 +19,7 @@
 #include "t2_plan.h"
 #include "modeadapt_kernels.h"
 #include "ule_kernels.h"
+#include "mpe_kernels.h"
 #include "gse_kernels.h"
 #include "t2mi_kernels.h"
 #include "t2mi_out_kernels.h"
@@ -2310,6 +2311,136 @@ extern "C" int dvbt2ll_ule_run_host(dvbt2ll_ule *h, const void *pdu, int64_t pdu
 }
 
 extern "C" void dvbt2ll_ule_destroy(dvbt2ll_ule *h) { delete h; }
+
+// ============================================================================ MPE encapsulator
+// A handle beside the chain, built like the ULE one: scratch sized at create from max_pdus, no stream state, all passes
+// of a run on the caller's stream (mpe_kernels.hip), the result on the device until get_result.
+struct dvbt2ll_mpe {
+  DeviceCtx ctx;
+  dvbt2ll_mpe_params p{};
+  MpeDev dev;
+  DevBuf scratch, pdu_tmp, off_tmp, out_tmp;
+  hipEvent_t done = nullptr;     // the last run; a run on another stream waits for it (the scratch is shared)
+  hipStream_t last = nullptr;
+  bool ran = false;
+  ~dvbt2ll_mpe() {
+    if (done) { (void)hipSetDevice(ctx.device); (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+  }
+};
+
+static bool mpe_params_ok(const dvbt2ll_mpe_params &p) {
+  if (p.pid < 0 || p.pid > 0x1FFE) return false;
+  if ((p.mac_mode != 0 && p.mac_mode != 1) || (p.packing != 0 && p.packing != 1)) return false;
+  if (p.max_pdu_bytes < 1 || p.max_pdu_bytes >= ((int64_t)1 << 31)) return false;
+  return p.max_pdus >= 1 && p.max_pdus <= (1 << 24);   // 2^24 sections of 23 packets: below 2^32 packets
+}
+
+extern "C" int dvbt2ll_mpe_create(const dvbt2ll_mpe_params *p, int device, dvbt2ll_mpe **out) {
+  if (!p || !out) return DVBT2LL_EINVAL;
+  *out = nullptr;
+  if (!mpe_params_ok(*p)) return DVBT2LL_EINVAL;
+  std::unique_ptr<dvbt2ll_mpe> h(new (std::nothrow) dvbt2ll_mpe());
+  if (!h) return DVBT2LL_ENOMEM;
+  h->p = *p;
+  int r = h->ctx.init(device);
+  if (r) return r;
+  MpeDev &d = h->dev;
+  d.pid = p->pid;
+  d.mac_mode = p->mac_mode;
+  d.packing = p->packing;
+  memcpy(d.mac, p->mac, 6);
+  d.max_pdus = (uint32_t)p->max_pdus;
+  if (h->scratch.ensure(mpe_layout(d, nullptr))) return DVBT2LL_ENOMEM;
+  (void)mpe_layout(d, h->scratch.p);
+  std::vector<uint32_t> tab(MPE_TAB_WORDS);
+  mpe_host_tables(tab.data());
+  HIP_TRY(hipMemcpy(d.tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d.res, 0, (MPE_R_WORDS + 2) * 8));
+  HIP_TRY(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+  *out = h.release();
+  return DVBT2LL_OK;
+}
+
+static int mpe_run_args(const dvbt2ll_mpe *h, const void *pdu, int64_t pdu_len, const uint32_t *off, int64_t n_pdus,
+                        const dvbt2ll_mpe_pos *start, void *out, int64_t cap, MpeRun &r) {
+  if (!h || !pdu || !off || !start || !out) return DVBT2LL_EINVAL;
+  if (pdu_len < 0 || pdu_len > h->p.max_pdu_bytes || n_pdus < 0 || n_pdus > h->p.max_pdus || cap < 0)
+    return DVBT2LL_EINVAL;
+  if (start->pdu < 0 || start->pdu > n_pdus || start->section_byte < 0 || start->section_byte >= MPE_MAX_SECTION ||
+      start->cc < 0 || start->cc > 15 || (start->section_byte && start->pdu == n_pdus))
+    return DVBT2LL_EINVAL;
+  r.pdu = (const uint8_t *)pdu;
+  r.pdu_len = (uint32_t)pdu_len;
+  r.off = off;
+  r.i0 = (uint32_t)start->pdu;
+  r.n = (uint32_t)(n_pdus - start->pdu);
+  r.section_byte = (uint32_t)start->section_byte;
+  r.cc = (uint32_t)start->cc;
+  r.out = (uint8_t *)out;
+  r.cap = (uint32_t)std::min<int64_t>(cap, (int64_t)1 << 30);
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_mpe_run_device(dvbt2ll_mpe *h, const void *pdu_dev, int64_t pdu_len, const uint32_t *off_dev,
+                                      int64_t n_pdus, const dvbt2ll_mpe_pos *start, void *out_dev,
+                                      int64_t out_cap_packets, int flush, void *stream) {
+  MpeRun r;
+  int e = mpe_run_args(h, pdu_dev, pdu_len, off_dev, n_pdus, start, out_dev, out_cap_packets, r);
+  if (e) return e;
+  r.flush = flush != 0;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->ctx.stream;
+  if (h->ran && h->last != st) HIP_TRY(hipStreamWaitEvent(st, h->done, 0));
+  HIP_TRY(mpe_launch(h->dev, r, st));
+  HIP_TRY(hipEventRecord(h->done, st));
+  h->last = st;
+  h->ran = true;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_mpe_get_result(dvbt2ll_mpe *h, dvbt2ll_mpe_result *res) {
+  if (!h || !res) return DVBT2LL_EINVAL;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  uint64_t w[MPE_R_WORDS];
+  HIP_TRY(hipMemcpy(w, h->dev.res, sizeof w, hipMemcpyDeviceToHost));
+  memset(res, 0, sizeof *res);
+  res->resume.pdu = (int64_t)w[MPE_R_PDU];
+  res->resume.section_byte = (int)w[MPE_R_SECTION_BYTE];
+  res->resume.cc = (int)w[MPE_R_CC];
+  int64_t *c = &res->pdus_in;
+  for (int k = 0; k < 9; k++) c[k] = (int64_t)w[MPE_R_PDUS_IN + k];
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_mpe_run_host(dvbt2ll_mpe *h, const void *pdu, int64_t pdu_len, const uint32_t *off,
+                                    int64_t n_pdus, const dvbt2ll_mpe_pos *start, void *out, int64_t out_cap_packets,
+                                    int flush, dvbt2ll_mpe_result *res) {
+  MpeRun r;
+  if (!res) return DVBT2LL_EINVAL;
+  int e = mpe_run_args(h, pdu, pdu_len, off, n_pdus, start, out, out_cap_packets, r);
+  if (e) return e;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  // no more packets than the PDUs can become wherever the offsets put them, whatever the capacity says: the
+  // device buffer holds this capacity, and this capacity is what the run is given
+  const int64_t cap = (int64_t)std::min<uint64_t>(r.cap, mpe_packet_limit(h->dev, r.pdu_len, r.n));
+  if (h->pdu_tmp.ensure((size_t)std::max<int64_t>(pdu_len, 1))) return DVBT2LL_ENOMEM;
+  if (h->off_tmp.ensure((size_t)(n_pdus + 1) * 4)) return DVBT2LL_ENOMEM;
+  if (h->out_tmp.ensure((size_t)cap * 188 + 16)) return DVBT2LL_ENOMEM;
+  hipStream_t st = h->ctx.stream;
+  if (pdu_len) HIP_TRY(hipMemcpyAsync(h->pdu_tmp.p, pdu, (size_t)pdu_len, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->off_tmp.p, off, (size_t)(n_pdus + 1) * 4, hipMemcpyHostToDevice, st));
+  if ((e = dvbt2ll_mpe_run_device(h, h->pdu_tmp.p, pdu_len, (const uint32_t *)h->off_tmp.p, n_pdus, start,
+                                  h->out_tmp.p, cap, flush, st)))
+    return e;
+  if ((e = dvbt2ll_mpe_get_result(h, res))) return e;
+  if (res->ts_packets > 0)
+    HIP_TRY(hipMemcpy(out, h->out_tmp.p, (size_t)res->ts_packets * 188, hipMemcpyDeviceToHost));
+  return DVBT2LL_OK;
+}
+
+extern "C" void dvbt2ll_mpe_destroy(dvbt2ll_mpe *h) { delete h; }
 
 // ============================================================================ GSE encapsulator
 // A handle beside the chain, built like the ULE one: scratch sized at create from max_pdus and Kbch, no stream state,

@@ -13,6 +13,7 @@ from .t2mi import T2miDeframer, T2miResult  # noqa: F401
 from .t2mi_out import T2miFramer, T2miOutPos, T2miOutResult, AuxSlot  # noqa: F401
 from .modeadapt import ModeAdapter, ModeAdaptPos, ModeAdaptResult  # noqa: F401
 from .ule import UleEncapsulator, UlePos, UleResult  # noqa: F401
+from .mpe import MpeEncapsulator, MpePos, MpeResult  # noqa: F401
 from .gse import GseEncapsulator, GsePos, GseResult  # noqa: F401
 from .configs import CONFIGS, T2Config, ts_packets, ts_for_frames, bbframe_span  # noqa: F401
 from .configs import MPLP_CONFIGS, MplpConfig, PlpConfig  # noqa: F401

@@ -702,6 +702,111 @@ int dvbt2ll_ule_run_host(dvbt2ll_ule *h, const void *pdu, int64_t pdu_len, const
 void dvbt2ll_ule_destroy(dvbt2ll_ule *h);
 
 /* ---------------------------------------------------------------------------
+ * MPE encapsulator (Multi-Protocol Encapsulation, EN 301 192 clause 7): a device buffer of IP datagrams and a device
+ * offset table -> DSM-CC datagram_sections in 188-byte TS packets that the chain's TS input, the mode adapter and
+ * dvbt2ll_tx take as they are: the encapsulation DVB itself specifies for IP over a transport stream, the one deployed
+ * IP-over-DVB receivers and TS analysers read.  A handle of its own beside the chain: it holds scratch, no stream
+ * state.  Not built: LLC/SNAP, section_number > 0 (a datagram split over several sections), the checksum form
+ * (section_syntax_indicator 0), scrambling, MPE-FEC and time slicing, INT / PSI tables, adaptation-field stuffing.
+ * The reference has no MPE code, so all of this is PARITY UNPINNED, pinned by tests/mpe_ref.py's sequential
+ * restatement and its ISO/IEC 13818-1 section receiver.
+ *
+ * input      as the ULE handle's: pdu_dev holds pdu_len bytes (below 2^31); off_dev holds n_pdus + 1 uint32_t
+ *            offsets: PDU i is bytes [off[i], off[i + 1]), p bytes.  A PDU is skipped and counted in skipped_len when
+ *            off[i + 1] <= off[i], or off[i + 1] > pdu_len, or p > 4080 (a whole section is at most 4096 bytes); the
+ *            length is judged first.  It is skipped and counted in skipped_type when its first nibble is neither 4 nor
+ *            6: MPE without LLC/SNAP carries IP only, and there is no type table.  A skipped PDU contributes nothing;
+ *            every rule below speaks of the remaining (valid) PDUs only.  Nothing outside [pdu_dev, pdu_dev + pdu_len)
+ *            and the offset table is read, whatever the offsets say.  The offsets need not ascend: valid PDUs may
+ *            overlap or repeat, each is encapsulated as it stands, and the packets may then be more than the buffer's
+ *            bytes suggest.
+ * section    n = 12 + p + 4 bytes, section_length = n - 3; the smallest has 17 bytes.
+ *              byte 0        3E (table_id)
+ *              byte 1        B0 | (section_length >> 8): section_syntax_indicator 1, private_indicator 0, reserved 11,
+ *                            the length's high 4 bits
+ *              byte 2        section_length & FF
+ *              byte 3, 4     MAC_address_6, MAC_address_5: the address's last byte, then the one before it
+ *              byte 5        C1: reserved 11, payload_scrambling_control 00, address_scrambling_control 00,
+ *                            LLC_SNAP_flag 0, current_next_indicator 1
+ *              byte 6, 7     section_number 0, last_section_number 0
+ *              byte 8 .. 11  MAC_address_4, _3, _2, _1: byte 11 is the address's first byte
+ *              byte 12 ..    the datagram
+ *              last 4        CRC_32, big-endian, over every section byte before it (polynomial 0x04C11DB7, initial
+ *                            value 0xFFFFFFFF, no reflection, no final XOR: the CRC the ULE encapsulator writes and
+ *                            the T2-MI deframer checks)
+ * MAC        mac_mode 0: every section carries mac.  mac_mode 1: an IPv4 datagram (first nibble 4) of at least 20
+ *            bytes whose byte 16 is in 224 .. 239 carries 01:00:5e:(b17 & 7f):b18:b19; an IPv6 datagram (first nibble
+ *            6) of at least 40 bytes whose byte 24 is ff carries 33:33:b36:b37:b38:b39; any other carries mac.
+ * TS packets sync 47, TEI 0, PUSI, priority 0, pid, scrambling 00, adaptation_field_control 01; the continuity
+ *            counter is start.cc, plus one mod 16 per emitted packet; 184 payload bytes.  With PUSI = 1 the first
+ *            payload byte is the pointer_field: the payload bytes between it and the first section that starts in the
+ *            packet.
+ * packing=1  when a packet begins, R is the number of bytes of the current section not yet sent (0: the packet begins
+ *            with a new section); "next": another valid section follows in this call.
+ *              R >= 184: PUSI 0, 184 section bytes.   R = 183: PUSI 0, 183 bytes, FF (no pointer_field can point
+ *              inside the packet).
+ *              R <= 182 and next: PUSI 1, pointer_field R, the R bytes, then sections back to back: a new section
+ *              starts while at least one payload byte is free and next exists (its header may straddle into the
+ *              following packets, to which this list applies again); a section ending on the packet's last byte
+ *              closes the packet.
+ *              0 < R <= 183, no next, flush = 1: PUSI 0, R bytes, the rest FF.   R = 0, no next: no packet.
+ *              A PUSI packet left with free bytes and no next: with flush = 1 it is filled with FF; without flush it
+ *              is not emitted (its content depends on whether a section follows).
+ * packing=0  every section starts a packet behind pointer_field 0, with up to 183 bytes and the rest FF; later
+ *            packets of the same section have PUSI 0, min(R, 184) bytes and the rest FF.  A section takes
+ *            ceil((n + 1) / 184) packets.  Flush changes nothing except flushed.
+ * capacity   a call emits the longest prefix of determined packets that fits out_cap_packets and returns resume =
+ *            {pdu, section_byte, cc}: the index of the PDU whose section holds the first section byte not emitted,
+ *            how many of that section's bytes were emitted, the counter of the next packet; {n_pdus, 0, cc} when
+ *            nothing is left.  The next call passes resume as start, with a PDU list that begins at or before that
+ *            PDU.  A start with section_byte > 0 begins with R = n - section_byte of that section, whose CRC is
+ *            computed again (a section_byte that is not below n, or at a skipped PDU, is taken as 0).  Chained calls
+ *            at any split produce the single call's bytes.
+ * counters   pdus_in, sections, skipped_len, skipped_type, mapped_macs (the sections whose MAC came from the
+ *            datagram) cover the PDUs from start.pdu to before resume.pdu, so they add up over chained calls;
+ *            ts_packets, pusi_packets and pad_bytes (the FF bytes; a pointer_field is none) cover the packets emitted;
+ *            flushed is 1 when flush was set and nothing is left.
+ * bounds     nothing outside out_cap_packets x 188 bytes of out_dev is written.
+ * ------------------------------------------------------------------------- */
+typedef struct dvbt2ll_mpe dvbt2ll_mpe;
+typedef struct {
+  int pid;                               /* 0 .. 0x1FFE */
+  uint8_t mac[6];                        /* the MAC address, first byte first */
+  int mac_mode;                          /* 0: every section carries mac; 1: multicast datagrams carry their group's */
+  int packing;                           /* 0 / 1 */
+  int64_t max_pdu_bytes;                 /* largest pdu_len of a run, 1 .. 2^31 - 1 */
+  int max_pdus;                          /* largest n_pdus of a run, 1 .. 2^24 */
+} dvbt2ll_mpe_params;
+typedef struct {
+  int64_t pdu;                           /* a PDU index in [0, n_pdus] */
+  int section_byte;                      /* bytes of that PDU's section already emitted */
+  int cc;                                /* 0 .. 15: the next packet's continuity counter */
+} dvbt2ll_mpe_pos;
+typedef struct {
+  dvbt2ll_mpe_pos resume;
+  int64_t pdus_in, sections, skipped_len, skipped_type, mapped_macs, ts_packets, pusi_packets, pad_bytes, flushed;
+} dvbt2ll_mpe_result;
+/* DVBT2LL_EINVAL: a null pointer, pid / mac_mode / packing / the maxima out of range; DVBT2LL_EDEVICE without a GPU */
+int dvbt2ll_mpe_create(const dvbt2ll_mpe_params *p, int device, dvbt2ll_mpe **out);
+/* pdu_dev, off_dev on the device; start: {0, 0, cc} or a previous call's resume position in this list's PDU indices;
+ * out_dev: room for out_cap_packets x 188 bytes.  Asynchronous on stream (NULL: the handle's own); no host round trip.
+ * One run of a handle at a time: the next run call on another stream first waits for the previous one.
+ * DVBT2LL_EINVAL, nothing launched: a null pointer, pdu_len or n_pdus negative or above the create-time maxima, a
+ * negative capacity, start.pdu outside [0, n_pdus], section_byte negative or > 0 at n_pdus, cc outside 0 .. 15. */
+int dvbt2ll_mpe_run_device(dvbt2ll_mpe *h, const void *pdu_dev, int64_t pdu_len, const uint32_t *off_dev,
+                           int64_t n_pdus, const dvbt2ll_mpe_pos *start, void *out_dev, int64_t out_cap_packets,
+                           int flush, void *stream);
+/* synchronises with the last run and returns its result */
+int dvbt2ll_mpe_get_result(dvbt2ll_mpe *h, dvbt2ll_mpe_result *res);
+/* host buffers, synchronous: the PDUs and the table are copied in, the written packets are copied out.  The device
+ * output buffer holds out_cap_packets, or what n_pdus PDUs inside pdu_len bytes can become at the most if that is
+ * less. */
+int dvbt2ll_mpe_run_host(dvbt2ll_mpe *h, const void *pdu, int64_t pdu_len, const uint32_t *off, int64_t n_pdus,
+                         const dvbt2ll_mpe_pos *start, void *out, int64_t out_cap_packets, int flush,
+                         dvbt2ll_mpe_result *res);
+void dvbt2ll_mpe_destroy(dvbt2ll_mpe *h);
+
+/* ---------------------------------------------------------------------------
  * GSE encapsulator (Generic Stream Encapsulation, ETSI TS 102 606-1; EN 302 755 5.1.7): a device buffer of PDUs (IP
  * datagrams) and a device offset table -> one PLP's normal-mode BBFRAMEs with TS/GS = 10, in the layout
  * DVBT2LL_INPUT_BBFRAME reads (kbch / 8 bytes per BBFRAME, back to back): IP reaches IQ with no TS layer.  A handle
