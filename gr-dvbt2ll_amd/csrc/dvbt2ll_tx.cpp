@@ -36,6 +36,11 @@
 // multicast group the group's MAC, --packing 0 starts a packet per section.  The TS then goes through the chain's TS
 // input exactly as a TS file does.
 //
+// --input mpe-fec reads the same records and groups them on the GPU into MPE-FEC frames of --rows rows, up to
+// --data-columns application data columns and --rs-columns Reed-Solomon columns: MPE sections with real-time
+// parameters, then MPE-FEC sections (dvbt2ll_mpefec_run_host in chunks, continued from each call's resume position,
+// flushed at the end of the file).  --mac, --mac-from-dest and --packing as for --input mpe.
+//
 // --input gse reads the same records and wraps them on the GPU in GSE packets laid into normal-mode BBFRAMEs (TS 102
 // 606-1; dvbt2ll_gse_run_host in chunks, continued from each call's resume position, flushed at the end of the file).
 // --label / --label3 / --no-label choose the 6-byte, 3-byte or no label.  The BBFRAMEs then go through the chain's
@@ -115,7 +120,7 @@ void usage(FILE *f) {
                "                          inputmode reservedbiasbits l1scrambled inband; pilotgen:\n"
                "                          misogroup equalization bandwidth; bbheaderbch: tsrate)\n"
                "                          misogroup: 0 TX1, 1 TX2 (pilots only), 2 TX2 with MISO processing\n"
-               "  --input ts|bbframe|t2mi|ts-npd|ule|mpe|gse what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
+               "  --input ts|bbframe|t2mi|ts-npd|ule|mpe|mpe-fec|gse what --in holds: an MPEG-TS (default), packed unscrambled BBFRAMEs\n"
                "                          of kbch / 8 bytes each (single-PLP presets), or a TS carrying T2-MI\n"
                "                          (one file; single-PLP and --mplp presets)\n"
                "                          ts-npd: a TS adapted on the GPU to HEM BBFRAMEs with null-packet deletion\n"
@@ -123,12 +128,17 @@ void usage(FILE *f) {
                "                          the GPU in ULE SNDUs (RFC 4326) on --pid (single-PLP presets)\n"
                "                          mpe: the same records, wrapped on the GPU in MPE datagram_sections (EN 301 192)\n"
                "                          on --pid (single-PLP presets)\n"
+               "                          mpe-fec: the same records in MPE-FEC frames: MPE sections, then RS(255,191)\n"
+               "                          columns in MPE-FEC sections, on --pid (single-PLP presets)\n"
                "                          gse: the same records, wrapped on the GPU in GSE packets (TS 102 606-1) in\n"
                "                          normal-mode BBFRAMEs (single-PLP presets)\n"
                "  --label aa:bb:cc:dd:ee:ff | --label3 aa:bb:cc | --no-label\n"
                "                          --input gse: the 6-byte label (default 02:00:48:55:4c:4b), a 3-byte one, none\n"
                "  --mac aa:bb:cc:dd:ee:ff --input ule / mpe: the destination / MAC address (default 02:00:48:55:4c:4b)\n"
                "  --mac-from-dest         --input mpe: a datagram to a multicast group carries the group's MAC\n"
+               "  --rows R                --input mpe-fec: rows of a frame's tables, 256 / 512 / 768 / 1024 (default 1024)\n"
+               "  --data-columns D        --input mpe-fec: the application data columns a frame may fill, 1 .. 191 (default 191)\n"
+               "  --rs-columns K          --input mpe-fec: the RS columns sent, 1 .. 64 (default 64)\n"
                "  --no-dest               --input ule: SNDUs without a destination address (D = 1)\n"
                "  --packing 0|1           --input ule / mpe: pack SNDUs / sections back to back (default 1) or one per packet start\n"
                "  --pids A,B,...          --input ts-npd: the PIDs of the next PLP of the preset (repeat per PLP;\n"
@@ -675,6 +685,103 @@ FILE *run_mpe(const std::string &in_path, int pid, const uint8_t *mac, int mac_m
   return ts;
 }
 
+constexpr int kInputMpeFec = 7;   // --input mpe-fec (the chain itself runs in DVBT2LL_INPUT_TS)
+
+// --input mpe-fec: the file's length-prefixed PDUs -> the MPE-FEC encapsulator in chunks -> a temporary TS file, which
+// the caller reads as it reads a TS file.  Returns the file rewound, or nullptr.
+FILE *run_mpefec(const std::string &in_path, int pid, const uint8_t *mac, int mac_mode, int packing, int rows, int dcols,
+                 int kcols, int device) {
+  const size_t chunk = 4 << 20, max_pdus = 65536;   // PDU bytes and PDUs per encapsulator call
+  dvbt2ll_mpefec_params up;
+  std::memset(&up, 0, sizeof(up));
+  up.pid = pid;
+  std::memcpy(up.mac, mac, 6);
+  up.mac_mode = mac_mode;
+  up.packing = packing;
+  up.max_pdu_bytes = (int64_t)chunk + 65536;
+  up.max_pdus = (int)max_pdus;
+  up.rows = rows;
+  up.data_columns = dcols;
+  up.rs_columns = kcols;
+  up.max_frames = 256;
+  dvbt2ll_mpefec *enc = nullptr;
+  int st = dvbt2ll_mpefec_create(&up, device, &enc);
+  if (st) { std::fprintf(stderr, "dvbt2ll_tx: mpe-fec: %s\n", dvbt2ll_strerror(st)); return nullptr; }
+  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
+  FILE *ts = std::tmpfile();
+  if (!fin || !ts) {
+    std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : "a temporary file", std::strerror(errno));
+    dvbt2ll_mpefec_destroy(enc);
+    return nullptr;
+  }
+  std::vector<uint8_t> pdus, out;
+  std::vector<uint32_t> off(1, 0);
+  dvbt2ll_mpefec_pos pos = {0, 0, 0, 0, 0};
+  dvbt2ll_mpefec_result tot;
+  std::memset(&tot, 0, sizeof(tot));
+  bool eof = false;
+  while (!st) {
+    while (!eof && pdus.size() < chunk && off.size() <= max_pdus) {
+      uint8_t lb[2];
+      if (std::fread(lb, 1, 2, fin) != 2) { eof = true; break; }
+      const size_t len = ((size_t)lb[0] << 8) | lb[1], old = pdus.size();
+      pdus.resize(old + len);
+      if (len && std::fread(pdus.data() + old, 1, len, fin) != len) { pdus.resize(old); eof = true; break; }   // a cut record
+      off.push_back((uint32_t)pdus.size());
+    }
+    const int64_t n = (int64_t)off.size() - 1;
+    // the records lie side by side in pdus: two successive frames hold more than a table's bytes, which bounds the
+    // frames, and so this many packets hold all the sections
+    const int64_t fr = std::min<int64_t>(std::min<int64_t>(up.max_frames, n), 2 * (int64_t)pdus.size() / ((int64_t)dcols * rows + 1) + 2);
+    const int64_t bytes = (int64_t)pdus.size() + 16 * n + fr * kcols * (rows + 16);
+    const int64_t cap = packing ? bytes / 183 + 2 : bytes / 184 + n + fr * kcols + 1;
+    out.resize((size_t)cap * 188);
+    const uint8_t none = 0;
+    dvbt2ll_mpefec_result res;
+    if ((st = dvbt2ll_mpefec_run_host(enc, pdus.empty() ? &none : pdus.data(), (int64_t)pdus.size(), off.data(), n,
+                                      &pos, out.data(), cap, eof, &res)))
+      break;
+    tot.pdus_in += res.pdus_in;
+    tot.sections += res.sections;
+    tot.fec_sections += res.fec_sections;
+    tot.frames += res.frames;
+    tot.skipped_len += res.skipped_len;
+    tot.skipped_type += res.skipped_type;
+    tot.mapped_macs += res.mapped_macs;
+    tot.ts_packets += res.ts_packets;
+    tot.pusi_packets += res.pusi_packets;
+    tot.pad_bytes += res.pad_bytes;
+    tot.flushed = res.flushed;   // the last call's
+    if (res.ts_packets && std::fwrite(out.data(), 188, (size_t)res.ts_packets, ts) != (size_t)res.ts_packets) { st = -1; break; }
+    // continue from the resume position: drop the PDUs before it
+    const uint32_t cut = off[(size_t)res.resume.pdu];
+    pdus.erase(pdus.begin(), pdus.begin() + cut);
+    off.erase(off.begin(), off.begin() + (size_t)res.resume.pdu);
+    for (uint32_t &o : off) o -= cut;
+    const bool stuck = res.resume.pdu == 0 && res.ts_packets == 0;
+    pos = res.resume;
+    pos.pdu = 0;
+    if (eof && (off.size() == 1 || stuck)) break;
+    // nothing consumed and no room to read on: give up, not loop
+    if (stuck && (pdus.size() >= chunk || off.size() > max_pdus)) {
+      std::fprintf(stderr, "dvbt2ll_tx: mpe-fec: no packet completes within %zu bytes / %zu records\n", pdus.size(), off.size() - 1);
+      st = -1;
+      break;
+    }
+  }
+  if (st) std::fprintf(stderr, "dvbt2ll_tx: mpe-fec run failed: %s\n", dvbt2ll_strerror(st));
+  std::fprintf(stderr, "dvbt2ll_tx: mpe-fec: pdus_in %lld, sections %lld, fec_sections %lld, frames %lld, skipped_len %lld, "
+               "skipped_type %lld, mapped_macs %lld, ts_packets %lld, pusi_packets %lld, pad_bytes %lld, flushed %lld\n",
+               (long long)tot.pdus_in, (long long)tot.sections, (long long)tot.fec_sections, (long long)tot.frames,
+               (long long)tot.skipped_len, (long long)tot.skipped_type, (long long)tot.mapped_macs,
+               (long long)tot.ts_packets, (long long)tot.pusi_packets, (long long)tot.pad_bytes, (long long)tot.flushed);
+  if (fin != stdin) std::fclose(fin);
+  dvbt2ll_mpefec_destroy(enc);
+  if (st) { std::fclose(ts); return nullptr; }
+  std::rewind(ts);
+  return ts;
+}
+
 constexpr int kInputGse = 5;   // --input gse (the chain itself runs in DVBT2LL_INPUT_BBFRAME)
 
 // --input gse: the file's length-prefixed PDUs -> the GSE encapsulator in chunks -> a temporary file of BBFRAMEs, which
@@ -867,6 +974,7 @@ int main(int argc, char **argv) {
   std::vector<std::vector<int>> pids;
   uint8_t mac[6] = {0x02, 0x00, 0x48, 0x55, 0x4C, 0x4B};   // the flowgraph's ule_source
   int ule_d_bit = 0, ule_packing = 1, mpe_mac_mode = 0;
+  int fec_rows = 1024, fec_dcols = 191, fec_kcols = 64;
   uint8_t gse_label[6] = {0x02, 0x00, 0x48, 0x55, 0x4C, 0x4B};
   int gse_label_len = 6;
   T2miOut gw;
@@ -901,6 +1009,7 @@ int main(int argc, char **argv) {
       else if (v == "ts-npd") input = kInputTsNpd;
       else if (v == "ule") input = kInputUle;
       else if (v == "mpe") input = kInputMpe;
+      else if (v == "mpe-fec") input = kInputMpeFec;
       else if (v == "gse") input = kInputGse;
       else { std::fprintf(stderr, "dvbt2ll_tx: unknown input %s\n", v.c_str()); return 2; }
     } else if (a == "--pid") pid = (int)std::strtol(next(), nullptr, 0);
@@ -933,6 +1042,9 @@ int main(int argc, char **argv) {
     else if (a == "--no-dest") ule_d_bit = 1;
     else if (a == "--mac-from-dest") mpe_mac_mode = 1;
     else if (a == "--packing") ule_packing = std::atoi(next());
+    else if (a == "--rows") fec_rows = std::atoi(next());
+    else if (a == "--data-columns") fec_dcols = std::atoi(next());
+    else if (a == "--rs-columns") fec_kcols = std::atoi(next());
     else if (a == "--plp-id") plp_ids.push_back((int)std::strtol(next(), nullptr, 0));
     else if (a == "--t2mi-out") gw.path = next();
     else if (a == "--t2mi-pid") gw.pid = (int)std::strtol(next(), nullptr, 0);
@@ -946,13 +1058,13 @@ int main(int argc, char **argv) {
   }
 
   T2miOut *gwp = gw.path.empty() ? nullptr : &gw;
-  if (gwp && !print_params && (input == DVBT2LL_INPUT_TS || input == kInputUle || input == kInputMpe)) {
+  if (gwp && !print_params && (input == DVBT2LL_INPUT_TS || input == kInputUle || input == kInputMpe || input == kInputMpeFec)) {
     std::fprintf(stderr, "dvbt2ll_tx: --t2mi-out needs an input that yields BBFRAMEs: --input bbframe, ts-npd, gse or t2mi\n");
     return 2;
   }
   if (!mplp.empty()) {
-    if (input == DVBT2LL_INPUT_BBFRAME || input == kInputUle || input == kInputMpe || input == kInputGse) {
-      std::fprintf(stderr, "dvbt2ll_tx: --input bbframe / ule / mpe / gse takes a single-PLP preset\n");
+    if (input == DVBT2LL_INPUT_BBFRAME || input == kInputUle || input == kInputMpe || input == kInputMpeFec || input == kInputGse) {
+      std::fprintf(stderr, "dvbt2ll_tx: --input bbframe / ule / mpe / mpe-fec / gse takes a single-PLP preset\n");
       return 2;
     }
     for (auto &q : kMplpPresets)
@@ -993,8 +1105,9 @@ int main(int argc, char **argv) {
   dvbt2ll_chain_info info;
   // (the info after set_input: it then counts whole BBFRAMEs)
   const bool tsnpd = input == kInputTsNpd, ule = input == kInputUle, mpe = input == kInputMpe, gse = input == kInputGse;
+  const bool mpefec = input == kInputMpeFec;
   const bool t2mi = input == kInputT2mi || tsnpd;
-  if (ule || mpe) input = DVBT2LL_INPUT_TS;   // the encapsulator's TS is read as a TS file is
+  if (ule || mpe || mpefec) input = DVBT2LL_INPUT_TS;   // the encapsulator's TS is read as a TS file is
   if (gse) input = DVBT2LL_INPUT_BBFRAME;   // the encapsulator's BBFRAMEs are read as a BBFRAME file is
   if ((st = dvbt2ll_chain_set_input(h, -1, t2mi ? DVBT2LL_INPUT_BBFRAME : input)) || (st = dvbt2ll_chain_get_info(h, &info)) ||
       (st = dvbt2ll_chain_set_output(h, gain, fmt))) {
@@ -1016,9 +1129,10 @@ int main(int argc, char **argv) {
   }
   FILE *fin = ule ? run_ule(in_path, pid, ule_d_bit, mac, ule_packing, device)
                   : mpe ? run_mpe(in_path, pid, mac, mpe_mac_mode, ule_packing, device)
+                  : mpefec ? run_mpefec(in_path, pid, mac, mpe_mac_mode, ule_packing, fec_rows, fec_dcols, fec_kcols, device)
                   : gse ? run_gse(h, in_path, gse_label_len, gse_label, device)
                   : in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
-  if ((ule || mpe || gse) && !fin) {
+  if ((ule || mpe || mpefec || gse) && !fin) {
     if (gwp) gwp->close();
     dvbt2ll_chain_destroy(h);
     return 1;

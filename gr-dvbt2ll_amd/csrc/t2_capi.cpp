@@ -20,6 +20,7 @@
 #include "modeadapt_kernels.h"
 #include "ule_kernels.h"
 #include "mpe_kernels.h"
+#include "mpefec_kernels.h"
 #include "gse_kernels.h"
 #include "t2mi_kernels.h"
 #include "t2mi_out_kernels.h"
@@ -2441,6 +2442,161 @@ extern "C" int dvbt2ll_mpe_run_host(dvbt2ll_mpe *h, const void *pdu, int64_t pdu
 }
 
 extern "C" void dvbt2ll_mpe_destroy(dvbt2ll_mpe *h) { delete h; }
+
+// ============================================================================ MPE-FEC encapsulator
+// A handle beside the chain, built like the MPE one: scratch sized at create from max_pdus and max_frames (the frames'
+// tables and RS columns), no stream state, all passes of a run on the caller's stream (mpefec_kernels.hip).
+struct dvbt2ll_mpefec {
+  DeviceCtx ctx;
+  dvbt2ll_mpefec_params p{};
+  MfDev dev;
+  DevBuf scratch, pdu_tmp, off_tmp, out_tmp;
+  hipEvent_t done = nullptr;     // the last run; a run on another stream waits for it (the scratch is shared)
+  hipStream_t last = nullptr;
+  bool ran = false;
+  ~dvbt2ll_mpefec() {
+    if (done) { (void)hipSetDevice(ctx.device); (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+  }
+};
+
+static bool mpefec_params_ok(const dvbt2ll_mpefec_params &p) {
+  if (p.pid < 0 || p.pid > 0x1FFE) return false;
+  if ((p.mac_mode != 0 && p.mac_mode != 1) || (p.packing != 0 && p.packing != 1)) return false;
+  if (p.max_pdu_bytes < 1 || p.max_pdu_bytes >= ((int64_t)1 << 31)) return false;
+  if (p.max_pdus < 1 || p.max_pdus > (1 << 24)) return false;
+  if (p.rows != 256 && p.rows != 512 && p.rows != 768 && p.rows != 1024) return false;
+  if (p.data_columns < 1 || p.data_columns > MF_DATA_COLS || p.rs_columns < 1 || p.rs_columns > MF_RS_COLS) return false;
+  return p.max_frames >= 1 && p.max_frames <= (1 << 16);
+}
+
+extern "C" int dvbt2ll_mpefec_create(const dvbt2ll_mpefec_params *p, int device, dvbt2ll_mpefec **out) {
+  if (!p || !out) return DVBT2LL_EINVAL;
+  *out = nullptr;
+  if (!mpefec_params_ok(*p)) return DVBT2LL_EINVAL;
+  std::unique_ptr<dvbt2ll_mpefec> h(new (std::nothrow) dvbt2ll_mpefec());
+  if (!h) return DVBT2LL_ENOMEM;
+  h->p = *p;
+  int r = h->ctx.init(device);
+  if (r) return r;
+  MfDev &d = h->dev;
+  d.pid = p->pid;
+  d.mac_mode = p->mac_mode;
+  d.packing = p->packing;
+  memcpy(d.mac, p->mac, 6);
+  d.rows = (uint32_t)p->rows;
+  d.D = (uint32_t)p->data_columns;
+  d.K = (uint32_t)p->rs_columns;
+  d.max_pdus = (uint32_t)p->max_pdus;
+  d.max_frames = (uint32_t)p->max_frames;
+  // a frame holds a datagram or more: no more frames than PDUs; one frame past max_frames is computed as well
+  d.max_items = d.max_pdus + std::min(d.max_frames + 1, d.max_pdus) * d.K;
+  if (h->scratch.ensure(mf_layout(d, nullptr))) return DVBT2LL_ENOMEM;
+  (void)mf_layout(d, h->scratch.p);
+  std::vector<uint32_t> tab(MF_TAB_WORDS), rstab(MF_RS_WORDS);
+  mf_host_tables(tab.data(), rstab.data());
+  HIP_TRY(hipMemcpy(d.tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.rstab, rstab.data(), rstab.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d.res, 0, (MF_R_WORDS + MF_CTL_WORDS / 2) * 8));
+  HIP_TRY(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+  *out = h.release();
+  return DVBT2LL_OK;
+}
+
+static int mpefec_run_args(const dvbt2ll_mpefec *h, const void *pdu, int64_t pdu_len, const uint32_t *off,
+                           int64_t n_pdus, const dvbt2ll_mpefec_pos *start, void *out, int64_t cap, MfRun &r) {
+  if (!h || !pdu || !off || !start || !out) return DVBT2LL_EINVAL;
+  if (pdu_len < 0 || pdu_len > h->p.max_pdu_bytes || n_pdus < 0 || n_pdus > h->p.max_pdus || cap < 0)
+    return DVBT2LL_EINVAL;
+  // a frame holds at most D x rows datagrams (of one byte each) and K RS columns: no frame has a section past that
+  const int64_t sections = (int64_t)h->p.data_columns * h->p.rows + h->p.rs_columns;
+  if (start->pdu < 0 || start->pdu > n_pdus || start->section < 0 || start->section >= sections ||
+      start->section_byte < 0 || start->section_byte >= MF_MAX_SECTION || start->cc < 0 || start->cc > 15 ||
+      start->frame < 0 || start->frame > 0xFFF || ((start->section || start->section_byte) && start->pdu == n_pdus))
+    return DVBT2LL_EINVAL;
+  r.pdu = (const uint8_t *)pdu;
+  r.pdu_len = (uint32_t)pdu_len;
+  r.off = off;
+  r.i0 = (uint32_t)start->pdu;
+  r.n = (uint32_t)(n_pdus - start->pdu);
+  r.section = (uint32_t)start->section;
+  r.section_byte = (uint32_t)start->section_byte;
+  r.cc = (uint32_t)start->cc;
+  r.frame = (uint32_t)start->frame;
+  r.out = (uint8_t *)out;
+  r.cap = (uint32_t)std::min<int64_t>(cap, (int64_t)1 << 30);
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_mpefec_run_device(dvbt2ll_mpefec *h, const void *pdu_dev, int64_t pdu_len,
+                                         const uint32_t *off_dev, int64_t n_pdus, const dvbt2ll_mpefec_pos *start,
+                                         void *out_dev, int64_t out_cap_packets, int flush, void *stream) {
+  MfRun r;
+  int e = mpefec_run_args(h, pdu_dev, pdu_len, off_dev, n_pdus, start, out_dev, out_cap_packets, r);
+  if (e) return e;
+  r.flush = flush != 0;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->ctx.stream;
+  if (h->ran && h->last != st) HIP_TRY(hipStreamWaitEvent(st, h->done, 0));
+  HIP_TRY(mf_launch(h->dev, r, st));
+  HIP_TRY(hipEventRecord(h->done, st));
+  h->last = st;
+  h->ran = true;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_mpefec_get_result(dvbt2ll_mpefec *h, dvbt2ll_mpefec_result *res) {
+  if (!h || !res) return DVBT2LL_EINVAL;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  uint64_t w[MF_R_WORDS];
+  HIP_TRY(hipMemcpy(w, h->dev.res, sizeof w, hipMemcpyDeviceToHost));
+  memset(res, 0, sizeof *res);
+  res->resume.pdu = (int64_t)w[MF_R_PDU];
+  res->resume.section = (int)w[MF_R_SECTION];
+  res->resume.section_byte = (int)w[MF_R_SECTION_BYTE];
+  res->resume.cc = (int)w[MF_R_CC];
+  res->resume.frame = (int)w[MF_R_FRAME];
+  res->pdus_in = (int64_t)w[MF_R_PDUS_IN];
+  res->sections = (int64_t)w[MF_R_SECTIONS];
+  res->fec_sections = (int64_t)w[MF_R_FEC_SECTIONS];
+  res->frames = (int64_t)w[MF_R_FRAMES];
+  res->skipped_len = (int64_t)w[MF_R_SKIPPED_LEN];
+  res->skipped_type = (int64_t)w[MF_R_SKIPPED_TYPE];
+  res->mapped_macs = (int64_t)w[MF_R_MAPPED];
+  res->ts_packets = (int64_t)w[MF_R_TS_PACKETS];
+  res->pusi_packets = (int64_t)w[MF_R_PUSI];
+  res->pad_bytes = (int64_t)w[MF_R_PAD];
+  res->flushed = (int64_t)w[MF_R_FLUSHED];
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_mpefec_run_host(dvbt2ll_mpefec *h, const void *pdu, int64_t pdu_len, const uint32_t *off,
+                                       int64_t n_pdus, const dvbt2ll_mpefec_pos *start, void *out,
+                                       int64_t out_cap_packets, int flush, dvbt2ll_mpefec_result *res) {
+  MfRun r;
+  if (!res) return DVBT2LL_EINVAL;
+  int e = mpefec_run_args(h, pdu, pdu_len, off, n_pdus, start, out, out_cap_packets, r);
+  if (e) return e;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  // no more packets than the PDUs can become wherever the offsets put them, whatever the capacity says
+  const int64_t cap = (int64_t)std::min<uint64_t>(r.cap, mf_packet_limit(h->dev, r.pdu_len, r.n));
+  if (h->pdu_tmp.ensure((size_t)std::max<int64_t>(pdu_len, 1))) return DVBT2LL_ENOMEM;
+  if (h->off_tmp.ensure((size_t)(n_pdus + 1) * 4)) return DVBT2LL_ENOMEM;
+  if (h->out_tmp.ensure((size_t)cap * 188 + 16)) return DVBT2LL_ENOMEM;
+  hipStream_t st = h->ctx.stream;
+  if (pdu_len) HIP_TRY(hipMemcpyAsync(h->pdu_tmp.p, pdu, (size_t)pdu_len, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->off_tmp.p, off, (size_t)(n_pdus + 1) * 4, hipMemcpyHostToDevice, st));
+  if ((e = dvbt2ll_mpefec_run_device(h, h->pdu_tmp.p, pdu_len, (const uint32_t *)h->off_tmp.p, n_pdus, start,
+                                     h->out_tmp.p, cap, flush, st)))
+    return e;
+  if ((e = dvbt2ll_mpefec_get_result(h, res))) return e;
+  if (res->ts_packets > 0)
+    HIP_TRY(hipMemcpy(out, h->out_tmp.p, (size_t)res->ts_packets * 188, hipMemcpyDeviceToHost));
+  return DVBT2LL_OK;
+}
+
+extern "C" void dvbt2ll_mpefec_destroy(dvbt2ll_mpefec *h) { delete h; }
 
 // ============================================================================ GSE encapsulator
 // A handle beside the chain, built like the ULE one: scratch sized at create from max_pdus and Kbch, no stream state,

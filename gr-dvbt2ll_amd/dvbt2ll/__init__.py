@@ -14,6 +14,7 @@ from .t2mi_out import T2miFramer, T2miOutPos, T2miOutResult, AuxSlot  # noqa: F4
 from .modeadapt import ModeAdapter, ModeAdaptPos, ModeAdaptResult  # noqa: F401
 from .ule import UleEncapsulator, UlePos, UleResult  # noqa: F401
 from .mpe import MpeEncapsulator, MpePos, MpeResult  # noqa: F401
+from .mpefec import MpeFecEncapsulator, MpeFecPos, MpeFecResult  # noqa: F401
 from .gse import GseEncapsulator, GsePos, GseResult  # noqa: F401
 from .configs import CONFIGS, T2Config, ts_packets, ts_for_frames, bbframe_span  # noqa: F401
 from .configs import MPLP_CONFIGS, MplpConfig, PlpConfig  # noqa: F401

@@ -149,6 +149,24 @@ class _MpeResult(ctypes.Structure):
         "flushed")]
 
 
+class _MpeFecParams(ctypes.Structure):
+    _fields_ = [("pid", ctypes.c_int), ("mac", ctypes.c_uint8 * 6), ("mac_mode", ctypes.c_int),
+                ("packing", ctypes.c_int), ("max_pdu_bytes", ctypes.c_int64), ("max_pdus", ctypes.c_int),
+                ("rows", ctypes.c_int), ("data_columns", ctypes.c_int), ("rs_columns", ctypes.c_int),
+                ("max_frames", ctypes.c_int)]
+
+
+class _MpeFecPos(ctypes.Structure):
+    _fields_ = [("pdu", ctypes.c_int64), ("section", ctypes.c_int), ("section_byte", ctypes.c_int),
+                ("cc", ctypes.c_int), ("frame", ctypes.c_int)]
+
+
+class _MpeFecResult(ctypes.Structure):
+    _fields_ = [("resume", _MpeFecPos)] + [(n, ctypes.c_int64) for n in (
+        "pdus_in", "sections", "fec_sections", "frames", "skipped_len", "skipped_type", "mapped_macs", "ts_packets",
+        "pusi_packets", "pad_bytes", "flushed")]
+
+
 class _GseParams(ctypes.Structure):
     _fields_ = [("kbch", ctypes.c_int), ("framesize", ctypes.c_int), ("rate", ctypes.c_int),
                 ("sis_mis", ctypes.c_int), ("isi", ctypes.c_int), ("label_len", ctypes.c_int),
@@ -220,6 +238,7 @@ EXPORTS += ["dvbt2ll_modeadapt_" + f for f in ("create", "params_from_chain", "r
                                                "destroy")]
 EXPORTS += ["dvbt2ll_ule_" + f for f in ("create", "run_device", "get_result", "run_host", "destroy")]
 EXPORTS += ["dvbt2ll_mpe_" + f for f in ("create", "run_device", "get_result", "run_host", "destroy")]
+EXPORTS += ["dvbt2ll_mpefec_" + f for f in ("create", "run_device", "get_result", "run_host", "destroy")]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create", "get_info", "run_device", "run_streams", "run_host", "set_output", "set_slots", "set_graph", "set_timing",
                                            "get_timing", "debug_codewords", "debug_cell_pairs", "debug_cells",
                                            "synchronize", "sync_errors",
@@ -340,6 +359,13 @@ def lib():
                                        ctypes.POINTER(_MpeResult)]
     L.dvbt2ll_mpe_destroy.argtypes = [vp]
     L.dvbt2ll_mpe_destroy.restype = None
+    L.dvbt2ll_mpefec_create.argtypes = [ctypes.POINTER(_MpeFecParams), ci, ctypes.POINTER(vp)]
+    L.dvbt2ll_mpefec_run_device.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(_MpeFecPos), vp, i64, ci, vp]
+    L.dvbt2ll_mpefec_get_result.argtypes = [vp, ctypes.POINTER(_MpeFecResult)]
+    L.dvbt2ll_mpefec_run_host.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(_MpeFecPos), vp, i64, ci,
+                                          ctypes.POINTER(_MpeFecResult)]
+    L.dvbt2ll_mpefec_destroy.argtypes = [vp]
+    L.dvbt2ll_mpefec_destroy.restype = None
     L.dvbt2ll_gse_create.argtypes = [ctypes.POINTER(_GseParams), ci, ctypes.POINTER(vp)]
     L.dvbt2ll_gse_params_from_chain.argtypes = [vp, ci, ctypes.POINTER(_GseParams)]
     L.dvbt2ll_gse_run_device.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(_GsePos), vp, i64, ci, vp]

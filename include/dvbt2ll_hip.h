@@ -707,7 +707,8 @@ void dvbt2ll_ule_destroy(dvbt2ll_ule *h);
  * dvbt2ll_tx take as they are: the encapsulation DVB itself specifies for IP over a transport stream, the one deployed
  * IP-over-DVB receivers and TS analysers read.  A handle of its own beside the chain: it holds scratch, no stream
  * state.  Not built: LLC/SNAP, section_number > 0 (a datagram split over several sections), the checksum form
- * (section_syntax_indicator 0), scrambling, MPE-FEC and time slicing, INT / PSI tables, adaptation-field stuffing.
+ * (section_syntax_indicator 0), scrambling, time slicing, INT / PSI tables, adaptation-field stuffing (MPE-FEC: the
+ * dvbt2ll_mpefec handle below).
  * The reference has no MPE code, so all of this is PARITY UNPINNED, pinned by tests/mpe_ref.py's sequential
  * restatement and its ISO/IEC 13818-1 section receiver.
  *
@@ -805,6 +806,108 @@ int dvbt2ll_mpe_run_host(dvbt2ll_mpe *h, const void *pdu, int64_t pdu_len, const
                          const dvbt2ll_mpe_pos *start, void *out, int64_t out_cap_packets, int flush,
                          dvbt2ll_mpe_result *res);
 void dvbt2ll_mpe_destroy(dvbt2ll_mpe *h);
+
+/* ---------------------------------------------------------------------------
+ * MPE-FEC encapsulator: the MPE encapsulator's input -> per MPE-FEC frame its MPE sections (with real-time
+ * parameters), then Reed-Solomon columns in MPE-FEC sections, in 188-byte TS packets, so that a receiver can rebuild
+ * datagrams lost to TS packet errors; a receiver that knows nothing of MPE-FEC still reads every datagram.  A handle of
+ * its own beside the chain: it holds scratch, no stream state.  The rules are this project's reading of EN 301 192
+ * clause 9, written without the standard at hand; the reference has no MPE-FEC code, so all of this is PARITY
+ * UNPINNED, pinned by tests/mpefec_ref.py's sequential restatement and its independent receiver.
+ * Not built: time slicing (delta_t as a time, burst scheduling with null packets, the time_slice_fec_identifier
+ * descriptor with INT / PSI tables), datagrams split over frames or sections, LLC/SNAP, per-frame data_columns or
+ * rs_columns, interleaved MPE and MPE-FEC sections, GNU Radio adapters and distributed variants.
+ *
+ * input      the MPE handle's (pdu_dev, off_dev, the skip rules and skipped_len / skipped_type), and a PDU is also
+ *            skipped into skipped_len when p > min(4080, D x rows).  With rows, D = data_columns, K = rs_columns:
+ *            C = D x rows.
+ * frames     the frames partition the call's PDU index range from start.pdu.  A frame takes successive valid PDUs
+ *            while the sum of their lengths stays <= C; it ends just behind its last datagram, and a later frame
+ *            begins there: skipped PDUs in front of a frame's first datagram belong to that frame and contribute
+ *            nothing.  A frame is closed when a further valid PDU of the call does not fit, or when flush = 1 and the
+ *            list ends with at least one datagram in it.  An open frame emits nothing, not even its MPE sections, so
+ *            where a call's list ends never changes the partition.
+ * table      the application data table A has 191 x rows bytes: the frame's m datagrams back to back from address 0,
+ *            U bytes in all, then zeros.  Address a is column a / rows, row a mod rows.
+ * RS         GF(2^8) with x^8 + x^4 + x^3 + x^2 + 1 (0x11D), lambda = 02, g(x) = prod (x + lambda^i), i = 0 .. 63.
+ *            Row r's data symbols are d_c = A[c x rows + r], c = 0 .. 190; par_0 .. par_63 are the coefficients of
+ *            (sum d_c x^(254 - c)) mod g(x), par_k that of x^(63 - k); RS column k, row r, is par_k: the 255-symbol
+ *            row vanishes at lambda^0 .. lambda^63.  Only RS columns 0 .. K - 1 are sent (K < 64: puncturing).
+ *            d_190 = 01 alone gives g_63 .. g_0 = c1 0a ff 3a .. e4 f2 f5; d_0 = 01 alone gives 8f 2f 0f 0e .. 96 8b.
+ * sections   a closed frame sends its m MPE sections, then K MPE-FEC sections.  RT (bytes 8 .. 11, big-endian) =
+ *            delta_t << 20 | table_boundary << 19 | frame_boundary << 18 | address; delta_t is the frame's cyclic
+ *            index, (start.frame + the frames closed before it in the call) & 0xFFF: time slicing is not used.
+ *              MPE section j: the MPE handle's 12 + p + 4 bytes, but bytes 8 .. 11 hold RT with table_boundary =
+ *              (j == m - 1), frame_boundary 0, address = the datagram's first byte in A.  Bytes 3, 4 carry MAC bytes
+ *              6, 5 by mac_mode, and mapped_macs counts as before.
+ *              MPE-FEC section k, rows + 16 bytes: 78; B0 | L >> 8, L & FF with L = rows + 13; padding_columns =
+ *              191 - ceil(U / rows); FF; FF (reserved 1s, current_next_indicator 1); section_number k;
+ *              last_section_number K - 1; RT with table_boundary = frame_boundary = (k == K - 1), address = k x rows;
+ *              RS column k, row 0 first; CRC_32 as the MPE section's.
+ * TS packets the MPE handle's rules for either packing value, over the whole section sequence; the sections of
+ *            successive frames pack back to back.  "next": another section of a closed frame follows in this call.
+ * capacity   a call emits the longest prefix of determined packets that fits out_cap_packets, of the first
+ *            max_frames closed frames.  Where a closed frame follows them, no packet that begins behind the last byte
+ *            of frame max_frames is emitted: the packet that frame ends in holds the next frame's first bytes (the
+ *            handle computes that frame as well, to know them, so its scratch holds max_frames + 1 frames), and the
+ *            flush does not apply.  resume = {pdu, section, section_byte, cc,
+ *            frame}: the first PDU index of the frame that holds the first section byte not emitted, which of that
+ *            frame's sections (0 .. m + K - 1) holds it, how many of that section's bytes were emitted, the next
+ *            packet's counter, that frame's index; with every closed frame sent, {the open frame's first index, or
+ *            n_pdus when no datagram is left; 0; 0; cc; the next frame's index}.  A start inside a frame recomputes
+ *            that frame from its first PDU, parity included.  Where the frame the start names is not closed in this
+ *            call, nothing is emitted and resume = start.  A start.section that is not below m + K is taken as
+ *            section 0, byte 0; a section_byte that is not below that section's length as 0.  Chained calls at any
+ *            list split, any capacity and any max_frames produce the single call's bytes.
+ * counters   pdus_in, sections (MPE), fec_sections, frames, skipped_len, skipped_type, mapped_macs cover the frames
+ *            wholly sent: the PDUs from start.pdu to before resume.pdu, so they add up over chained calls; ts_packets,
+ *            pusi_packets, pad_bytes cover the packets emitted; flushed is 1 when flush was set and resume.pdu is
+ *            n_pdus.
+ * bounds     nothing outside out_cap_packets x 188 bytes of out_dev is written.
+ * ------------------------------------------------------------------------- */
+typedef struct dvbt2ll_mpefec dvbt2ll_mpefec;
+typedef struct {
+  int pid;                               /* 0 .. 0x1FFE */
+  uint8_t mac[6];                        /* the MAC address, first byte first */
+  int mac_mode;                          /* 0: every section carries mac; 1: multicast datagrams carry their group's */
+  int packing;                           /* 0 / 1 */
+  int64_t max_pdu_bytes;                 /* largest pdu_len of a run, 1 .. 2^31 - 1 */
+  int max_pdus;                          /* largest n_pdus of a run, 1 .. 2^24 */
+  int rows;                              /* 256, 512, 768 or 1024 */
+  int data_columns;                      /* D, 1 .. 191: the application data columns a frame may fill */
+  int rs_columns;                        /* K, 1 .. 64: the RS columns sent */
+  int max_frames;                        /* 1 .. 2^16: the most frames one call closes.  The scratch holds (max_frames + 1)
+                                          * x (D + K) x rows bytes of tables and RS columns (16 MiB at 64, rows 1024, D 191,
+                                          * K 64; about 17 GB at 2^16): create returns DVBT2LL_ENOMEM where that is too much */
+} dvbt2ll_mpefec_params;
+typedef struct {
+  int64_t pdu;                           /* a frame's first PDU index, in [0, n_pdus] */
+  int section;                           /* a section of that frame */
+  int section_byte;                      /* bytes of that section already emitted */
+  int cc;                                /* 0 .. 15: the next packet's continuity counter */
+  int frame;                             /* 0 .. 4095: that frame's index */
+} dvbt2ll_mpefec_pos;
+typedef struct {
+  dvbt2ll_mpefec_pos resume;
+  int64_t pdus_in, sections, fec_sections, frames, skipped_len, skipped_type, mapped_macs, ts_packets, pusi_packets,
+      pad_bytes, flushed;
+} dvbt2ll_mpefec_result;
+/* DVBT2LL_EINVAL: a null pointer or a parameter out of range; DVBT2LL_EDEVICE without a GPU */
+int dvbt2ll_mpefec_create(const dvbt2ll_mpefec_params *p, int device, dvbt2ll_mpefec **out);
+/* as dvbt2ll_mpe_run_device.  DVBT2LL_EINVAL, nothing launched: a null pointer, pdu_len or n_pdus negative or above the
+ * create-time maxima, a negative capacity, start.pdu outside [0, n_pdus], section outside 0 .. D x rows + K - 1 (a
+ * frame of one-byte datagrams has D x rows MPE sections; every resume position lies inside), section_byte outside
+ * 0 .. 4095, section or section_byte > 0 at n_pdus, cc outside 0 .. 15, frame outside 0 .. 4095. */
+int dvbt2ll_mpefec_run_device(dvbt2ll_mpefec *h, const void *pdu_dev, int64_t pdu_len, const uint32_t *off_dev,
+                              int64_t n_pdus, const dvbt2ll_mpefec_pos *start, void *out_dev, int64_t out_cap_packets,
+                              int flush, void *stream);
+/* synchronises with the last run and returns its result */
+int dvbt2ll_mpefec_get_result(dvbt2ll_mpefec *h, dvbt2ll_mpefec_result *res);
+/* host buffers, synchronous, as dvbt2ll_mpe_run_host */
+int dvbt2ll_mpefec_run_host(dvbt2ll_mpefec *h, const void *pdu, int64_t pdu_len, const uint32_t *off, int64_t n_pdus,
+                            const dvbt2ll_mpefec_pos *start, void *out, int64_t out_cap_packets, int flush,
+                            dvbt2ll_mpefec_result *res);
+void dvbt2ll_mpefec_destroy(dvbt2ll_mpefec *h);
 
 /* ---------------------------------------------------------------------------
  * GSE encapsulator (Generic Stream Encapsulation, ETSI TS 102 606-1; EN 302 755 5.1.7): a device buffer of PDUs (IP
