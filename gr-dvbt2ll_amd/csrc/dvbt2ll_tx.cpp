@@ -46,6 +46,15 @@
 // --label / --label3 / --no-label choose the 6-byte, 3-byte or no label.  The BBFRAMEs then go through the chain's
 // BBFRAME input exactly as a BBFRAME file does.
 //
+// --mux period=P,weight=W,psi-weight=V[,pcr-pid=N,pcr-weight=K,ts-rate=R] (with --input ule, mpe or mpe-fec) sends the
+// encapsulated TS through the TS multiplexer before the chain reads it (dvbt2ll_tsmux_run_host, in calls of whole
+// periods: at least 8192 slots, each continuing from the previous one's resume position, until the encapsulated TS is
+// used up).  Input 0 is the encapsulated TS with W slots of P, and it is the fill input; input 1 is a one-programme
+// PAT / PMT carousel (dvbt2ll_psi_build: transport_stream_id 1, version 0) with V slots, looped.  --program,
+// --pmt-pid and --stream-type choose the PMT's values; its one stream is --pid, without descriptors.  pcr-pid adds K PCR
+// packets per period (default 1) from a clock that starts at 0 and runs at ts-rate bits per second, and becomes the
+// PMT's PCR_PID.
+//
 // --t2mi-out FILE --t2mi-pid N [--t2mi-stream-id S] writes, next to the IQ, the T2-MI transport stream of exactly the
 // frames encoded (dvbt2ll_t2mi_out_run_host per batch, each batch continuing from the previous one's next position;
 // no auxiliary slots): what a gateway would send to remote modulators, which produce the same IQ from it with
@@ -141,6 +150,13 @@ void usage(FILE *f) {
                "  --rs-columns K          --input mpe-fec: the RS columns sent, 1 .. 64 (default 64)\n"
                "  --no-dest               --input ule: SNDUs without a destination address (D = 1)\n"
                "  --packing 0|1           --input ule / mpe: pack SNDUs / sections back to back (default 1) or one per packet start\n"
+               "  --mux period=P,weight=W,psi-weight=V[,pcr-pid=N,pcr-weight=K,ts-rate=R]\n"
+               "                          --input ule / mpe / mpe-fec: multiplex the encapsulated TS (W slots of P, and the\n"
+               "                          free ones) with a PAT / PMT carousel (V slots), null packets and, with pcr-pid,\n"
+               "                          K PCR packets per period of a TS of R bit/s\n"
+               "  --program N             --mux: the PMT's program_number (default 1)\n"
+               "  --pmt-pid N             --mux: the PMT's PID (default 0x20)\n"
+               "  --stream-type N         --mux: the stream_type of --pid in the PMT (default 0x0D)\n"
                "  --pids A,B,...          --input ts-npd: the PIDs of the next PLP of the preset (repeat per PLP;\n"
                "                          default: every PID but 0x1FFF)\n"
                "  --pid N                 --input t2mi / ule / mpe: the PID of the T2-MI stream / SNDUs / sections (default 4096)\n"
@@ -782,6 +798,105 @@ FILE *run_mpefec(const std::string &in_path, int pid, const uint8_t *mac, int ma
   return ts;
 }
 
+// --mux: the encapsulated TS (a temporary file) -> the TS multiplexer with a PSI carousel -> another temporary file,
+// which the caller reads in its place.  Closes ts; returns the new file rewound, or nullptr.
+struct MuxOpt {
+  bool on = false;
+  int period = 0, weight = 0, psi_weight = 0, pcr_pid = -1, pcr_weight = 1;
+  long long ts_rate = 0;
+  int program = 1, pmt_pid = 0x20, stream_type = 0x0D;
+};
+
+bool parse_mux(const char *arg, MuxOpt &m) {
+  m.on = true;
+  for (const char *c = arg; *c;) {
+    const char *eq = std::strchr(c, '='), *end = std::strchr(c, ',');
+    if (!end) end = c + std::strlen(c);
+    if (!eq || eq > end) return false;
+    const std::string key(c, eq - c);
+    const long long v = std::strtoll(eq + 1, nullptr, 0);
+    if (key == "period") m.period = (int)v;
+    else if (key == "weight") m.weight = (int)v;
+    else if (key == "psi-weight") m.psi_weight = (int)v;
+    else if (key == "pcr-pid") m.pcr_pid = (int)v;
+    else if (key == "pcr-weight") m.pcr_weight = (int)v;
+    else if (key == "ts-rate") m.ts_rate = v;
+    else return false;
+    c = *end ? end + 1 : end;
+  }
+  return true;
+}
+
+FILE *run_mux(FILE *ts, const MuxOpt &m, int pid, int device) {
+  std::vector<uint8_t> in;
+  uint8_t buf[188 * 256];
+  for (size_t got; (got = std::fread(buf, 1, sizeof buf, ts)) > 0;) in.insert(in.end(), buf, buf + got);
+  std::fclose(ts);
+  dvbt2ll_psi_params pp;
+  std::memset(&pp, 0, sizeof(pp));
+  pp.transport_stream_id = 1;
+  pp.n_programs = 1;
+  pp.programs[0].program_number = m.program;
+  pp.programs[0].pmt_pid = m.pmt_pid;
+  pp.programs[0].pcr_pid = m.pcr_pid >= 0 ? m.pcr_pid : 0x1FFF;
+  pp.programs[0].n_streams = 1;
+  pp.programs[0].streams[0].stream_type = m.stream_type;
+  pp.programs[0].streams[0].pid = pid;
+  const int64_t npsi = dvbt2ll_psi_build(&pp, nullptr, 0);
+  if (npsi < 0 || m.pmt_pid == pid || m.pcr_pid == m.pmt_pid) { std::fprintf(stderr, "dvbt2ll_tx: mux: bad --program / --pmt-pid / --stream-type / --pid\n"); return nullptr; }
+  std::vector<uint8_t> psi((size_t)npsi * 188);
+  (void)dvbt2ll_psi_build(&pp, psi.data(), npsi);
+  dvbt2ll_tsmux_params up;
+  std::memset(&up, 0, sizeof(up));
+  up.n_inputs = 2;
+  up.period = m.period;
+  up.weight[0] = m.weight;
+  up.weight[1] = m.psi_weight;
+  up.loop[1] = 1;
+  up.fill_input = 0;
+  up.pcr_pid = m.pcr_pid >= 0 ? m.pcr_pid : -1;
+  up.pcr_weight = m.pcr_pid >= 0 ? m.pcr_weight : 0;
+  up.ticks_per_period = m.pcr_pid >= 0 ? dvbt2ll_tsmux_ticks_per_period(m.period, m.ts_rate) : 0;
+  const int64_t per_call = m.period > 0 ? (int64_t)m.period * std::max(1, 8192 / m.period) : 1;   // whole periods
+  up.max_out_packets = (int)per_call;
+  dvbt2ll_tsmux *mux = nullptr;
+  int st = dvbt2ll_tsmux_create(&up, device, &mux);
+  if (st) { std::fprintf(stderr, "dvbt2ll_tx: mux: %s\n", dvbt2ll_strerror(st)); return nullptr; }
+  FILE *out_f = std::tmpfile();
+  if (!out_f) { std::fprintf(stderr, "dvbt2ll_tx: cannot open a temporary file: %s\n", std::strerror(errno)); dvbt2ll_tsmux_destroy(mux); return nullptr; }
+  std::vector<uint8_t> out((size_t)per_call * 188);
+  dvbt2ll_tsmux_pos pos;
+  std::memset(&pos, 0, sizeof(pos));
+  const int64_t total = (int64_t)(in.size() / 188);
+  int64_t used = 0, slots = 0, psi_packets = 0, in_free = 0, pcr = 0, nulls = 0, sync = 0;
+  while (!st && used < total) {
+    // a call of per_call slots takes at most per_call packets, so it is given that window of the encapsulated TS
+    const void *ptr[DVBT2LL_TSMUX_INPUTS] = {in.data() + (size_t)used * 188, psi.data()};
+    const int64_t n_in[DVBT2LL_TSMUX_INPUTS] = {std::min(per_call, total - used), npsi};
+    pos.next[0] = 0;
+    dvbt2ll_tsmux_result res;
+    if ((st = dvbt2ll_tsmux_run_host(mux, ptr, n_in, &pos, out.data(), per_call, &res))) break;
+    if (std::fwrite(out.data(), 188, (size_t)per_call, out_f) != (size_t)per_call) { st = -1; break; }
+    pos = res.resume;
+    used += res.consumed[0];
+    slots += per_call;
+    psi_packets += res.consumed[1];
+    in_free += res.fill_in_free;
+    pcr += res.pcr_packets;
+    nulls += res.null_packets;
+    sync += res.sync_errors;
+    if (res.consumed[0] == 0) { std::fprintf(stderr, "dvbt2ll_tx: mux: the schedule gives the input no slot\n"); st = -1; }
+  }
+  if (st) std::fprintf(stderr, "dvbt2ll_tx: mux run failed: %s\n", dvbt2ll_strerror(st));
+  std::fprintf(stderr, "dvbt2ll_tx: mux: slots %lld, consumed %lld, psi_packets %lld, fill_in_free %lld, pcr_packets %lld, "
+               "null_packets %lld, sync_errors %lld\n", (long long)slots, (long long)used, (long long)psi_packets,
+               (long long)in_free, (long long)pcr, (long long)nulls, (long long)sync);
+  dvbt2ll_tsmux_destroy(mux);
+  if (st) { std::fclose(out_f); return nullptr; }
+  std::rewind(out_f);
+  return out_f;
+}
+
 constexpr int kInputGse = 5;   // --input gse (the chain itself runs in DVBT2LL_INPUT_BBFRAME)
 
 // --input gse: the file's length-prefixed PDUs -> the GSE encapsulator in chunks -> a temporary file of BBFRAMEs, which
@@ -978,6 +1093,7 @@ int main(int argc, char **argv) {
   uint8_t gse_label[6] = {0x02, 0x00, 0x48, 0x55, 0x4C, 0x4B};
   int gse_label_len = 6;
   T2miOut gw;
+  MuxOpt mux;
   bool print_params = false;
   int64_t frames = -1;
   float gain = 1.f;
@@ -1045,6 +1161,11 @@ int main(int argc, char **argv) {
     else if (a == "--rows") fec_rows = std::atoi(next());
     else if (a == "--data-columns") fec_dcols = std::atoi(next());
     else if (a == "--rs-columns") fec_kcols = std::atoi(next());
+    else if (a == "--mux") {
+      if (!parse_mux(next(), mux)) { std::fprintf(stderr, "dvbt2ll_tx: bad --mux\n"); return 2; }
+    } else if (a == "--program") mux.program = (int)std::strtol(next(), nullptr, 0);
+    else if (a == "--pmt-pid") mux.pmt_pid = (int)std::strtol(next(), nullptr, 0);
+    else if (a == "--stream-type") mux.stream_type = (int)std::strtol(next(), nullptr, 0);
     else if (a == "--plp-id") plp_ids.push_back((int)std::strtol(next(), nullptr, 0));
     else if (a == "--t2mi-out") gw.path = next();
     else if (a == "--t2mi-pid") gw.pid = (int)std::strtol(next(), nullptr, 0);
@@ -1060,6 +1181,10 @@ int main(int argc, char **argv) {
   T2miOut *gwp = gw.path.empty() ? nullptr : &gw;
   if (gwp && !print_params && (input == DVBT2LL_INPUT_TS || input == kInputUle || input == kInputMpe || input == kInputMpeFec)) {
     std::fprintf(stderr, "dvbt2ll_tx: --t2mi-out needs an input that yields BBFRAMEs: --input bbframe, ts-npd, gse or t2mi\n");
+    return 2;
+  }
+  if (mux.on && input != kInputUle && input != kInputMpe && input != kInputMpeFec) {
+    std::fprintf(stderr, "dvbt2ll_tx: --mux needs --input ule, mpe or mpe-fec\n");
     return 2;
   }
   if (!mplp.empty()) {
@@ -1132,6 +1257,7 @@ int main(int argc, char **argv) {
                   : mpefec ? run_mpefec(in_path, pid, mac, mpe_mac_mode, ule_packing, fec_rows, fec_dcols, fec_kcols, device)
                   : gse ? run_gse(h, in_path, gse_label_len, gse_label, device)
                   : in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
+  if (mux.on && fin) fin = run_mux(fin, mux, pid, device);
   if ((ule || mpe || mpefec || gse) && !fin) {
     if (gwp) gwp->close();
     dvbt2ll_chain_destroy(h);

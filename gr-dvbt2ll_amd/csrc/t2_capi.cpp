@@ -21,6 +21,8 @@
 #include "ule_kernels.h"
 #include "mpe_kernels.h"
 #include "mpefec_kernels.h"
+#include "tsmux_kernels.h"
+#include "tsmux_plan.h"
 #include "gse_kernels.h"
 #include "t2mi_kernels.h"
 #include "t2mi_out_kernels.h"
@@ -2597,6 +2599,149 @@ extern "C" int dvbt2ll_mpefec_run_host(dvbt2ll_mpefec *h, const void *pdu, int64
 }
 
 extern "C" void dvbt2ll_mpefec_destroy(dvbt2ll_mpefec *h) { delete h; }
+
+// ============================================================================ TS multiplexer
+// A handle beside the chain, built like the MPE one: the schedule tables are made at create (tsmux_plan.cpp) and stay
+// on the device; a run is one kernel on the caller's stream (tsmux_kernels.hip) whose counters stay on the device
+// until get_result, which adds the resume position: that is arithmetic on the start position and the counters.
+struct dvbt2ll_tsmux {
+  DeviceCtx ctx;
+  dvbt2ll_tsmux_params p{};
+  TsmuxPlan plan;
+  TsmuxDev dev;
+  DevBuf table, pre, res, out_tmp;
+  DevBuf in_tmp[TSMUX_IN];
+  dvbt2ll_tsmux_pos start{};     // of the last run
+  int64_t n_in[TSMUX_IN] = {}, n_out = 0;
+  hipEvent_t done = nullptr;     // the last run; a run on another stream waits for it (the counters are shared)
+  hipStream_t last = nullptr;
+  bool ran = false;
+  ~dvbt2ll_tsmux() {
+    if (done) { (void)hipSetDevice(ctx.device); (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+  }
+};
+
+extern "C" int dvbt2ll_tsmux_create(const dvbt2ll_tsmux_params *p, int device, dvbt2ll_tsmux **out) {
+  if (!p || !out) return DVBT2LL_EINVAL;
+  *out = nullptr;
+  if (!tsmux_params_ok(*p)) return DVBT2LL_EINVAL;
+  std::unique_ptr<dvbt2ll_tsmux> h(new (std::nothrow) dvbt2ll_tsmux());
+  if (!h) return DVBT2LL_ENOMEM;
+  h->p = *p;
+  int r = h->ctx.init(device);
+  if (r) return r;
+  tsmux_plan(*p, h->plan);
+  if ((r = upload(h->table, h->plan.table)) || (r = upload(h->pre, h->plan.pre))) return r;
+  if (h->res.ensure(TSMUX_R_WORDS * 8)) return DVBT2LL_ENOMEM;
+  HIP_TRY(hipMemset(h->res.p, 0, TSMUX_R_WORDS * 8));
+  TsmuxDev &d = h->dev;
+  d.n = p->n_inputs;
+  d.owners = h->plan.owners;
+  d.fill = p->fill_input;
+  d.pcr_pid = p->pcr_pid;
+  d.period = (uint32_t)p->period;
+  for (int i = 0; i < p->n_inputs; i++) d.loop |= (uint32_t)p->loop[i] << i;
+  for (int e = 0; e < TSMUX_OWN; e++) d.w[e] = h->plan.w[e];
+  d.tpp = (unsigned long long)p->ticks_per_period;
+  d.tpp_q = d.tpp / d.period;
+  d.tpp_r = (uint32_t)(d.tpp % d.period);
+  d.table = h->table.as<uint8_t>();
+  d.pre = h->pre.as<uint32_t>();
+  d.res = h->res.as<unsigned long long>();
+  HIP_TRY(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+  *out = h.release();
+  return DVBT2LL_OK;
+}
+
+static int tsmux_run_args(const dvbt2ll_tsmux *h, const void *const *in, const int64_t *n_in,
+                          const dvbt2ll_tsmux_pos *start, void *out, int64_t n_out, TsmuxRun &r) {
+  if (!h || !in || !n_in || !start || !out) return DVBT2LL_EINVAL;
+  if (n_out < 0 || n_out > h->p.max_out_packets) return DVBT2LL_EINVAL;
+  if (start->phase < 0 || start->phase >= h->p.period || start->pcr_ticks < 0 || start->pcr_ticks >= TSMUX_PCR_WRAP)
+    return DVBT2LL_EINVAL;
+  for (int i = 0; i < h->p.n_inputs; i++) {
+    if (n_in[i] < 0 || n_in[i] > 0x7FFFFFFF || (n_in[i] > 0 && !in[i])) return DVBT2LL_EINVAL;
+    if (start->next[i] < 0 || start->next[i] > n_in[i]) return DVBT2LL_EINVAL;
+    r.in[i] = (const uint8_t *)in[i];
+    r.n_in[i] = (uint32_t)n_in[i];
+    r.next[i] = (uint32_t)start->next[i];
+  }
+  const uint32_t *row = &h->plan.pre[(size_t)start->phase * h->plan.owners];
+  for (int e = 0; e < h->plan.owners; e++) r.pre0[e] = row[e];
+  r.phase = (uint32_t)start->phase;
+  r.n_out = (uint32_t)n_out;
+  r.pcr_ticks = (unsigned long long)start->pcr_ticks;
+  r.out = (uint8_t *)out;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_tsmux_run_device(dvbt2ll_tsmux *h, const void *const *in_dev, const int64_t *n_in,
+                                        const dvbt2ll_tsmux_pos *start, void *out_dev, int64_t n_out, void *stream) {
+  TsmuxRun r;
+  int e = tsmux_run_args(h, in_dev, n_in, start, out_dev, n_out, r);
+  if (e) return e;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->ctx.stream;
+  if (h->ran && h->last != st) HIP_TRY(hipStreamWaitEvent(st, h->done, 0));
+  HIP_TRY(tsmux_launch(h->dev, r, st));
+  HIP_TRY(hipEventRecord(h->done, st));
+  h->start = *start;
+  h->n_out = n_out;
+  for (int i = 0; i < TSMUX_IN; i++) h->n_in[i] = i < h->p.n_inputs ? n_in[i] : 0;
+  h->last = st;
+  h->ran = true;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_tsmux_get_result(dvbt2ll_tsmux *h, dvbt2ll_tsmux_result *res) {
+  if (!h || !res) return DVBT2LL_EINVAL;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  uint64_t w[TSMUX_R_WORDS];
+  HIP_TRY(hipMemcpy(w, h->dev.res, sizeof w, hipMemcpyDeviceToHost));
+  memset(res, 0, sizeof *res);
+  for (int i = 0; i < TSMUX_IN; i++) {
+    res->consumed[i] = (int64_t)w[TSMUX_R_CONSUMED + i];
+    res->dry_slots[i] = (int64_t)w[TSMUX_R_DRY + i];
+    const int64_t nx = h->start.next[i] + res->consumed[i];
+    res->resume.next[i] = i < h->p.n_inputs && h->p.loop[i] ? (h->n_in[i] ? nx % h->n_in[i] : 0) : nx;
+  }
+  res->fill_in_free = (int64_t)w[TSMUX_R_FILL_IN_FREE];
+  res->pcr_packets = (int64_t)w[TSMUX_R_PCR];
+  res->null_packets = (int64_t)w[TSMUX_R_NULL];
+  res->sync_errors = (int64_t)w[TSMUX_R_SYNC];
+  const int64_t at = h->start.phase + h->n_out;
+  res->resume.phase = (int)(at % h->p.period);
+  // the periods passed are at most 2^24 + 1 and ticks_per_period is below 2^36
+  res->resume.pcr_ticks = (h->start.pcr_ticks + (at / h->p.period) * h->p.ticks_per_period) % TSMUX_PCR_WRAP;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_tsmux_run_host(dvbt2ll_tsmux *h, const void *const *in, const int64_t *n_in,
+                                      const dvbt2ll_tsmux_pos *start, void *out, int64_t n_out,
+                                      dvbt2ll_tsmux_result *res) {
+  TsmuxRun r;
+  if (!res) return DVBT2LL_EINVAL;
+  int e = tsmux_run_args(h, in, n_in, start, out, n_out, r);
+  if (e) return e;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
+  hipStream_t st = h->ctx.stream;
+  const void *dev_in[TSMUX_IN] = {};
+  for (int i = 0; i < h->p.n_inputs; i++) {
+    if (!n_in[i]) continue;
+    if (h->in_tmp[i].ensure((size_t)n_in[i] * 188)) return DVBT2LL_ENOMEM;
+    HIP_TRY(hipMemcpyAsync(h->in_tmp[i].p, in[i], (size_t)n_in[i] * 188, hipMemcpyHostToDevice, st));
+    dev_in[i] = h->in_tmp[i].p;
+  }
+  if (h->out_tmp.ensure((size_t)std::max<int64_t>(n_out, 1) * 188)) return DVBT2LL_ENOMEM;
+  if ((e = dvbt2ll_tsmux_run_device(h, dev_in, n_in, start, h->out_tmp.p, n_out, st))) return e;
+  if ((e = dvbt2ll_tsmux_get_result(h, res))) return e;
+  if (n_out > 0) HIP_TRY(hipMemcpy(out, h->out_tmp.p, (size_t)n_out * 188, hipMemcpyDeviceToHost));
+  return DVBT2LL_OK;
+}
+
+extern "C" void dvbt2ll_tsmux_destroy(dvbt2ll_tsmux *h) { delete h; }
 
 // ============================================================================ GSE encapsulator
 // A handle beside the chain, built like the ULE one: scratch sized at create from max_pdus and Kbch, no stream state,

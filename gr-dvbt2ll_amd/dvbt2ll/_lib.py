@@ -167,6 +167,41 @@ class _MpeFecResult(ctypes.Structure):
         "pusi_packets", "pad_bytes", "flushed")]
 
 
+TSMUX_INPUTS = 8      # DVBT2LL_TSMUX_INPUTS
+PSI_PROGRAMS, PSI_STREAMS, PSI_DESCRIPTOR_BYTES, PSI_ROUNDS = 8, 8, 64, 16   # DVBT2LL_PSI_*
+
+
+class _TsMuxParams(ctypes.Structure):
+    _fields_ = [("n_inputs", ctypes.c_int), ("period", ctypes.c_int), ("weight", ctypes.c_int * TSMUX_INPUTS),
+                ("loop", ctypes.c_int * TSMUX_INPUTS), ("fill_input", ctypes.c_int), ("pcr_pid", ctypes.c_int),
+                ("pcr_weight", ctypes.c_int), ("ticks_per_period", ctypes.c_int64), ("max_out_packets", ctypes.c_int)]
+
+
+class _TsMuxPos(ctypes.Structure):
+    _fields_ = [("phase", ctypes.c_int), ("pcr_ticks", ctypes.c_int64), ("next", ctypes.c_int64 * TSMUX_INPUTS)]
+
+
+class _TsMuxResult(ctypes.Structure):
+    _fields_ = [("resume", _TsMuxPos), ("consumed", ctypes.c_int64 * TSMUX_INPUTS),
+                ("dry_slots", ctypes.c_int64 * TSMUX_INPUTS)] + [(n, ctypes.c_int64) for n in (
+                    "fill_in_free", "pcr_packets", "null_packets", "sync_errors")]
+
+
+class _PsiStream(ctypes.Structure):
+    _fields_ = [("stream_type", ctypes.c_int), ("pid", ctypes.c_int), ("descriptor_len", ctypes.c_int),
+                ("descriptors", ctypes.c_uint8 * PSI_DESCRIPTOR_BYTES)]
+
+
+class _PsiProgram(ctypes.Structure):
+    _fields_ = [("program_number", ctypes.c_int), ("pmt_pid", ctypes.c_int), ("pcr_pid", ctypes.c_int),
+                ("n_streams", ctypes.c_int), ("streams", _PsiStream * PSI_STREAMS)]
+
+
+class _PsiParams(ctypes.Structure):
+    _fields_ = [("transport_stream_id", ctypes.c_int), ("version", ctypes.c_int), ("n_programs", ctypes.c_int),
+                ("programs", _PsiProgram * PSI_PROGRAMS)]
+
+
 class _GseParams(ctypes.Structure):
     _fields_ = [("kbch", ctypes.c_int), ("framesize", ctypes.c_int), ("rate", ctypes.c_int),
                 ("sis_mis", ctypes.c_int), ("isi", ctypes.c_int), ("label_len", ctypes.c_int),
@@ -239,6 +274,9 @@ EXPORTS += ["dvbt2ll_modeadapt_" + f for f in ("create", "params_from_chain", "r
 EXPORTS += ["dvbt2ll_ule_" + f for f in ("create", "run_device", "get_result", "run_host", "destroy")]
 EXPORTS += ["dvbt2ll_mpe_" + f for f in ("create", "run_device", "get_result", "run_host", "destroy")]
 EXPORTS += ["dvbt2ll_mpefec_" + f for f in ("create", "run_device", "get_result", "run_host", "destroy")]
+EXPORTS += ["dvbt2ll_tsmux_" + f for f in ("schedule", "ticks_per_period", "create", "run_device", "get_result",
+                                           "run_host", "destroy")]
+EXPORTS += ["dvbt2ll_psi_build"]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create", "get_info", "run_device", "run_streams", "run_host", "set_output", "set_slots", "set_graph", "set_timing",
                                            "get_timing", "debug_codewords", "debug_cell_pairs", "debug_cells",
                                            "synchronize", "sync_errors",
@@ -366,6 +404,19 @@ def lib():
                                           ctypes.POINTER(_MpeFecResult)]
     L.dvbt2ll_mpefec_destroy.argtypes = [vp]
     L.dvbt2ll_mpefec_destroy.restype = None
+    L.dvbt2ll_tsmux_schedule.argtypes = [ctypes.POINTER(_TsMuxParams), vp]
+    L.dvbt2ll_tsmux_ticks_per_period.argtypes = [ci, i64]
+    L.dvbt2ll_tsmux_ticks_per_period.restype = i64
+    L.dvbt2ll_tsmux_create.argtypes = [ctypes.POINTER(_TsMuxParams), ci, ctypes.POINTER(vp)]
+    L.dvbt2ll_tsmux_run_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(_TsMuxPos), vp,
+                                           i64, vp]
+    L.dvbt2ll_tsmux_get_result.argtypes = [vp, ctypes.POINTER(_TsMuxResult)]
+    L.dvbt2ll_tsmux_run_host.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(_TsMuxPos), vp,
+                                         i64, ctypes.POINTER(_TsMuxResult)]
+    L.dvbt2ll_tsmux_destroy.argtypes = [vp]
+    L.dvbt2ll_tsmux_destroy.restype = None
+    L.dvbt2ll_psi_build.argtypes = [ctypes.POINTER(_PsiParams), vp, i64]
+    L.dvbt2ll_psi_build.restype = i64
     L.dvbt2ll_gse_create.argtypes = [ctypes.POINTER(_GseParams), ci, ctypes.POINTER(vp)]
     L.dvbt2ll_gse_params_from_chain.argtypes = [vp, ci, ctypes.POINTER(_GseParams)]
     L.dvbt2ll_gse_run_device.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(_GsePos), vp, i64, ci, vp]

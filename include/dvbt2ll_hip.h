@@ -910,6 +910,145 @@ int dvbt2ll_mpefec_run_host(dvbt2ll_mpefec *h, const void *pdu, int64_t pdu_len,
 void dvbt2ll_mpefec_destroy(dvbt2ll_mpefec *h);
 
 /* ---------------------------------------------------------------------------
+ * TS multiplexer: up to 8 device buffers of 188-byte TS packets -> one constant-bit-rate TS on the device, with null
+ * packets where nothing is due and, if asked for, PCR packets: what turns the single-PID streams of the ULE / MPE /
+ * MPE-FEC handles and a PSI carousel (dvbt2ll_psi_build below) into a stream a deployed receiver or TS analyser can
+ * find its way in, and what the mode adapter then splits over the PLPs by PID.  A handle of its own beside the chain:
+ * it holds the schedule tables and the last run's counters, no stream state.  Which input a slot belongs to is a fixed
+ * periodic schedule, so every output packet is resolved on its own: no scan.  An input packet's bytes are never
+ * altered.  Not built: PCR restamping of inputs that carry their own PCR, continuity restamping, per-PID remapping,
+ * SDT / NIT / INT, section versions changing inside a carousel, GNU Radio adapters and distributed variants.  The
+ * reference has no multiplexer, so all of this is PARITY UNPINNED, pinned by tests/tsmux_ref.py's sequential
+ * restatement and its TS checker.
+ *
+ * schedule   the owners are the inputs 0 .. n - 1, the PCR generator (owner n, weight pcr_weight) and "null" (owner
+ *            n + 1, weight period - the sum of the others).  Owner e's k-th slot, k = 0 .. w_e - 1, is due at k / w_e
+ *            of the period.  All period (due, e) pairs are sorted by due time ascending (compared exactly: k w_f
+ *            against k' w_e), ties to the lower e; the m-th pair takes table slot m.  pre_e[t] is the number of
+ *            owner e's slots among table slots [0, t).  dvbt2ll_tsmux_schedule returns the table without a GPU.
+ * position   {phase, pcr_ticks, next[8]}: the table slot of the call's first output packet (0 .. period - 1); the
+ *            27 MHz clock at the start of the period that holds that slot, modulo W = 2^33 x 300; next[i], the index
+ *            of input i's next packet in the buffer passed (0 .. n_in[i]).
+ * a run      writes exactly n_out packets, whatever the inputs hold.  For output index m: dc = (phase + m) / period,
+ *            t = (phase + m) mod period, the owner e = table[t], and r_e(m) = dc w_e + pre_e[t] - pre_e[phase] is the
+ *            number of e's slots in this call before m.  avail_i = n_in[i] - next[i].
+ *              a non-loop input i (not the fill input): packet next[i] + r_i(m) when r_i(m) < avail_i, else the slot is
+ *                free and counted in dry_slots[i]
+ *              a loop input i: packet (next[i] + r_i(m)) mod n_in[i]; with n_in[i] = 0 the slot is free and counted in
+ *                dry_slots[i]
+ *              null: a free slot
+ *              PCR: 47, pcr_pid >> 8, pcr_pid & FF, 20 (adaptation field only, continuity counter 0: it does not
+ *                count on such packets); B7 (adaptation_field_length 183), 10 (PCR_flag); six bytes holding the
+ *                33-bit base, six 1 bits and the 9-bit extension; 176 x FF.  The clock is T = (pcr_ticks + dc
+ *                ticks_per_period + floor(t ticks_per_period / period)) mod W, base = T / 300, extension = T mod 300.
+ *              a free slot without a fill input: the null packet 47 1F FF 10, 184 x FF
+ *              with fill input f (loop[f] = 0): f's claims are its own slots and every free slot of the others, in
+ *                slot order.  The claim of rank c(m) = r_f(m) + r_null(m) + the sum over the non-loop inputs i != f
+ *                of max(0, r_i(m) - avail_i) + the sum over the empty loop inputs of r_i(m) carries packet next[f] +
+ *                c(m) when c(m) < avail_f; any other claim is a null packet (f's own slot is then counted in
+ *                dry_slots[f])
+ *            An input packet whose first byte is not 47 is consumed, counted in sync_errors and sent as a null
+ *            packet.
+ * result     resume: phase advanced by n_out mod period; pcr_ticks advanced by ((phase + n_out) / period)
+ *            ticks_per_period, mod W; next[i] advanced by consumed[i] (mod n_in[i] for a loop input).  consumed[i]:
+ *            the packets taken from input i, bad-sync ones included; dry_slots[i] as above; fill_in_free: the fill
+ *            input's packets carried in slots it does not own; pcr_packets; null_packets: every null packet written,
+ *            those replacing a bad-sync packet included; sync_errors.  Chained calls at any split of n_out, given the
+ *            same buffers and each call's resume position, produce the single call's bytes and summed counters.
+ * bounds     nothing outside n_out x 188 bytes of out_dev is written, nothing outside an input's n_in[i] x 188 bytes
+ *            is read.  Inputs and output may have any byte alignment.
+ * ------------------------------------------------------------------------- */
+#define DVBT2LL_TSMUX_INPUTS 8
+#define DVBT2LL_TSMUX_MAX_PERIOD 65536
+typedef struct dvbt2ll_tsmux dvbt2ll_tsmux;
+typedef struct {
+  int n_inputs;                          /* 1 .. 8 */
+  int period;                            /* slots of the schedule's period, 1 .. 65536 */
+  int weight[DVBT2LL_TSMUX_INPUTS];      /* slots per period of input i; 0 only for the fill input */
+  int loop[DVBT2LL_TSMUX_INPUTS];        /* 0 / 1: the input's buffer is a carousel, read round and round */
+  int fill_input;                        /* -1, or the index of an input with loop 0 that also takes the free slots */
+  int pcr_pid;                           /* -1: no PCR packets; else 0 .. 0x1FFE */
+  int pcr_weight;                        /* PCR packets per period: >= 1 with a PCR PID, else 0 */
+  int64_t ticks_per_period;              /* 27 MHz ticks that period slots last, 1 .. 2^36 - 1 (0 without a PCR PID) */
+  int max_out_packets;                   /* largest n_out of a run, 1 .. 2^24 */
+} dvbt2ll_tsmux_params;
+typedef struct {
+  int phase;                             /* 0 .. period - 1 */
+  int64_t pcr_ticks;                     /* 0 .. 2^33 x 300 - 1 */
+  int64_t next[DVBT2LL_TSMUX_INPUTS];    /* 0 .. n_in[i] */
+} dvbt2ll_tsmux_pos;
+typedef struct {
+  dvbt2ll_tsmux_pos resume;
+  int64_t consumed[DVBT2LL_TSMUX_INPUTS], dry_slots[DVBT2LL_TSMUX_INPUTS];
+  int64_t fill_in_free, pcr_packets, null_packets, sync_errors;
+} dvbt2ll_tsmux_result;
+/* host only: the schedule table of p, period owner indices (input i, n_inputs: PCR, n_inputs + 1: null).
+ * DVBT2LL_EINVAL: a null pointer, a value out of range, the weights and pcr_weight above period, a weight of 0 on an
+ * input that is not the fill input, a fill input that loops, pcr_weight / ticks_per_period that do not go with pcr_pid */
+int dvbt2ll_tsmux_schedule(const dvbt2ll_tsmux_params *p, uint8_t *owner);
+/* host only: round(period x 1504 x 27e6 / ts_bits_per_second), the ticks_per_period of a TS of that rate; -1 when
+ * period is outside 1 .. 65536 or the rate is not positive */
+int64_t dvbt2ll_tsmux_ticks_per_period(int period, int64_t ts_bits_per_second);
+/* DVBT2LL_EINVAL as dvbt2ll_tsmux_schedule; DVBT2LL_EDEVICE without a GPU */
+int dvbt2ll_tsmux_create(const dvbt2ll_tsmux_params *p, int device, dvbt2ll_tsmux **out);
+/* in_dev[i]: input i's n_in[i] packets on the device (entries from n_inputs on are ignored); out_dev: room for n_out x
+ * 188 bytes.  Asynchronous on stream (NULL: the handle's own); no host round trip.  One run of a handle at a time: the
+ * next run call on another stream first waits for the previous one.  DVBT2LL_EINVAL, nothing launched: a null handle,
+ * start or out_dev, a null in_dev[i] where n_in[i] > 0, n_in[i] negative or above 2^31 - 1, n_out negative or above
+ * max_out_packets, next[i] outside [0, n_in[i]], phase outside [0, period), pcr_ticks outside [0, 2^33 x 300) */
+int dvbt2ll_tsmux_run_device(dvbt2ll_tsmux *h, const void *const *in_dev, const int64_t *n_in,
+                             const dvbt2ll_tsmux_pos *start, void *out_dev, int64_t n_out, void *stream);
+/* synchronises with the last run and returns its result */
+int dvbt2ll_tsmux_get_result(dvbt2ll_tsmux *h, dvbt2ll_tsmux_result *res);
+/* host buffers, synchronous: the inputs are copied in, the n_out packets are copied out */
+int dvbt2ll_tsmux_run_host(dvbt2ll_tsmux *h, const void *const *in, const int64_t *n_in,
+                           const dvbt2ll_tsmux_pos *start, void *out, int64_t n_out, dvbt2ll_tsmux_result *res);
+void dvbt2ll_tsmux_destroy(dvbt2ll_tsmux *h);
+
+/* ---------------------------------------------------------------------------
+ * PSI builder (host only): a PAT and one PMT per programme (ISO/IEC 13818-1 2.4.4) as a carousel of TS packets for a
+ * loop input of the multiplexer.  The stream types and descriptors are the caller's, carried as they are.
+ *
+ * rounds     the buffer holds 16 rounds.  A round is the PAT (PID 0) in one packet, then each programme's PMT on its
+ *            pmt_pid in as many packets as it needs.  A section's first packet has PUSI 1 and pointer_field 00, later
+ *            ones carry 184 section bytes; the bytes behind the section's end are FF.  Every PID's continuity counter
+ *            runs on across the rounds, and after 16 rounds every PID has sent a multiple of 16 packets: the buffer
+ *            read round and round is a seamless stream, which is why the multiplexer needs no continuity logic.
+ * PAT        00, B0 | len >> 8, len & FF; transport_stream_id (2 bytes); C1 | version << 1; 00 00; per programme:
+ *            program_number (2 bytes), E0 | pmt_pid >> 8, pmt_pid & FF; CRC_32 (the MPE section's).  len counts the
+ *            bytes behind the length field, CRC_32 included.
+ * PMT        02, B0 | len >> 8, len & FF; program_number (2 bytes); C1 | version << 1; 00 00; E0 | pcr_pid >> 8,
+ *            pcr_pid & FF; F0 00 (no programme descriptors); per stream: stream_type, E0 | pid >> 8, pid & FF,
+ *            F0 | n >> 8, n & FF, the n descriptor bytes; CRC_32.
+ * ------------------------------------------------------------------------- */
+#define DVBT2LL_PSI_PROGRAMS 8
+#define DVBT2LL_PSI_STREAMS 8
+#define DVBT2LL_PSI_DESCRIPTOR_BYTES 64
+#define DVBT2LL_PSI_ROUNDS 16
+typedef struct {
+  int stream_type;                       /* 0 .. 255 */
+  int pid;                               /* 0 .. 0x1FFF */
+  int descriptor_len;                    /* 0 .. 64 */
+  uint8_t descriptors[DVBT2LL_PSI_DESCRIPTOR_BYTES];
+} dvbt2ll_psi_stream;
+typedef struct {
+  int program_number;                    /* 1 .. 65535 */
+  int pmt_pid;                           /* 0x10 .. 0x1FFE, distinct across the programmes */
+  int pcr_pid;                           /* 0 .. 0x1FFF; 0x1FFF: the programme has no PCR */
+  int n_streams;                         /* 0 .. 8 */
+  dvbt2ll_psi_stream streams[DVBT2LL_PSI_STREAMS];
+} dvbt2ll_psi_program;
+typedef struct {
+  int transport_stream_id;               /* 0 .. 65535 */
+  int version;                           /* 0 .. 31 */
+  int n_programs;                        /* 1 .. 8 */
+  dvbt2ll_psi_program programs[DVBT2LL_PSI_PROGRAMS];
+} dvbt2ll_psi_params;
+/* writes the carousel's packets to out (room for cap_packets x 188 bytes) and returns their number; with out NULL it
+ * returns the number only.  DVBT2LL_EINVAL: a null p, a value out of range, PMT PIDs that repeat, too small a capacity */
+int64_t dvbt2ll_psi_build(const dvbt2ll_psi_params *p, uint8_t *out, int64_t cap_packets);
+
+/* ---------------------------------------------------------------------------
  * GSE encapsulator (Generic Stream Encapsulation, ETSI TS 102 606-1; EN 302 755 5.1.7): a device buffer of PDUs (IP
  * datagrams) and a device offset table -> one PLP's normal-mode BBFRAMEs with TS/GS = 10, in the layout
  * DVBT2LL_INPUT_BBFRAME reads (kbch / 8 bytes per BBFRAME, back to back): IP reaches IQ with no TS layer.  A handle
