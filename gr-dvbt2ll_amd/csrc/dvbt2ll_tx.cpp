@@ -53,7 +53,9 @@
 // PAT / PMT carousel (dvbt2ll_psi_build: transport_stream_id 1, version 0) with V slots, looped.  --program,
 // --pmt-pid and --stream-type choose the PMT's values; its one stream is --pid, without descriptors.  pcr-pid adds K PCR
 // packets per period (default 1) from a clock that starts at 0 and runs at ts-rate bits per second, and becomes the
-// PMT's PCR_PID.
+// PMT's PCR_PID.  remap=FROM:TO (repeatable) sends input 0's packets of PID FROM out on PID TO (0x1FFF drops them); a
+// remap of --pid also changes the PID the PMT names.  restamp-cc gives input 0's output PID and the carousel's PIDs new
+// continuity counters, carried from call to call (dvbt2ll_tsmux_set_remux, dvbt2ll_tsmux_run_host_remux).
 //
 // --t2mi-out FILE --t2mi-pid N [--t2mi-stream-id S] writes, next to the IQ, the T2-MI transport stream of exactly the
 // frames encoded (dvbt2ll_t2mi_out_run_host per batch, each batch continuing from the previous one's next position;
@@ -74,6 +76,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "dvbt2ll_hip.h"
@@ -150,10 +153,11 @@ void usage(FILE *f) {
                "  --rs-columns K          --input mpe-fec: the RS columns sent, 1 .. 64 (default 64)\n"
                "  --no-dest               --input ule: SNDUs without a destination address (D = 1)\n"
                "  --packing 0|1           --input ule / mpe: pack SNDUs / sections back to back (default 1) or one per packet start\n"
-               "  --mux period=P,weight=W,psi-weight=V[,pcr-pid=N,pcr-weight=K,ts-rate=R]\n"
+               "  --mux period=P,weight=W,psi-weight=V[,pcr-pid=N,pcr-weight=K,ts-rate=R][,remap=FROM:TO]...[,restamp-cc]\n"
                "                          --input ule / mpe / mpe-fec: multiplex the encapsulated TS (W slots of P, and the\n"
                "                          free ones) with a PAT / PMT carousel (V slots), null packets and, with pcr-pid,\n"
-               "                          K PCR packets per period of a TS of R bit/s\n"
+               "                          K PCR packets per period of a TS of R bit/s; remap=FROM:TO moves a PID of the\n"
+               "                          encapsulated TS (0x1FFF drops it), restamp-cc renumbers the continuity counters\n"
                "  --program N             --mux: the PMT's program_number (default 1)\n"
                "  --pmt-pid N             --mux: the PMT's PID (default 0x20)\n"
                "  --stream-type N         --mux: the stream_type of --pid in the PMT (default 0x0D)\n"
@@ -805,6 +809,8 @@ struct MuxOpt {
   int period = 0, weight = 0, psi_weight = 0, pcr_pid = -1, pcr_weight = 1;
   long long ts_rate = 0;
   int program = 1, pmt_pid = 0x20, stream_type = 0x0D;
+  std::vector<std::pair<int, int>> remap;   // remap=FROM:TO, input 0's PIDs
+  bool restamp_cc = false;                  // new continuity counters for input 0 and the carousel
 };
 
 bool parse_mux(const char *arg, MuxOpt &m) {
@@ -812,8 +818,21 @@ bool parse_mux(const char *arg, MuxOpt &m) {
   for (const char *c = arg; *c;) {
     const char *eq = std::strchr(c, '='), *end = std::strchr(c, ',');
     if (!end) end = c + std::strlen(c);
+    if (std::string(c, end - c) == "restamp-cc") {
+      m.restamp_cc = true;
+      c = *end ? end + 1 : end;
+      continue;
+    }
     if (!eq || eq > end) return false;
     const std::string key(c, eq - c);
+    if (key == "remap") {
+      char *colon = nullptr;
+      const long from = std::strtol(eq + 1, &colon, 0);
+      if (!colon || *colon != ':' || colon > end) return false;
+      m.remap.emplace_back((int)from, (int)std::strtol(colon + 1, nullptr, 0));
+      c = *end ? end + 1 : end;
+      continue;
+    }
     const long long v = std::strtoll(eq + 1, nullptr, 0);
     if (key == "period") m.period = (int)v;
     else if (key == "weight") m.weight = (int)v;
@@ -841,9 +860,12 @@ FILE *run_mux(FILE *ts, const MuxOpt &m, int pid, int device) {
   pp.programs[0].pcr_pid = m.pcr_pid >= 0 ? m.pcr_pid : 0x1FFF;
   pp.programs[0].n_streams = 1;
   pp.programs[0].streams[0].stream_type = m.stream_type;
-  pp.programs[0].streams[0].pid = pid;
+  int out_pid = pid;   // the PID the encapsulated stream leaves with, which is the one the PMT names
+  for (const auto &e : m.remap)
+    if (e.first == pid) out_pid = e.second;
+  pp.programs[0].streams[0].pid = out_pid;
   const int64_t npsi = dvbt2ll_psi_build(&pp, nullptr, 0);
-  if (npsi < 0 || m.pmt_pid == pid || m.pcr_pid == m.pmt_pid) { std::fprintf(stderr, "dvbt2ll_tx: mux: bad --program / --pmt-pid / --stream-type / --pid\n"); return nullptr; }
+  if (npsi < 0 || m.pmt_pid == out_pid || m.pcr_pid == m.pmt_pid) { std::fprintf(stderr, "dvbt2ll_tx: mux: bad --program / --pmt-pid / --stream-type / --pid\n"); return nullptr; }
   std::vector<uint8_t> psi((size_t)npsi * 188);
   (void)dvbt2ll_psi_build(&pp, psi.data(), npsi);
   dvbt2ll_tsmux_params up;
@@ -862,6 +884,27 @@ FILE *run_mux(FILE *ts, const MuxOpt &m, int pid, int device) {
   dvbt2ll_tsmux *mux = nullptr;
   int st = dvbt2ll_tsmux_create(&up, device, &mux);
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: mux: %s\n", dvbt2ll_strerror(st)); return nullptr; }
+  const bool remux = !m.remap.empty() || m.restamp_cc;
+  if (remux) {
+    dvbt2ll_tsmux_remux rx;
+    std::memset(&rx, 0, sizeof(rx));
+    if (m.remap.size() > DVBT2LL_TSMUX_MAP) st = DVBT2LL_EINVAL;
+    for (size_t k = 0; !st && k < m.remap.size(); k++) {
+      rx.map[k].input = 0;
+      rx.map[k].from_pid = m.remap[k].first;
+      rx.map[k].to_pid = m.remap[k].second;
+      rx.n_map = (int)k + 1;
+    }
+    if (m.restamp_cc) {   // input 0's output PID, then the carousel's
+      rx.track_pid[0] = out_pid;
+      rx.track_pid[1] = 0;
+      rx.track_pid[2] = m.pmt_pid;
+      rx.n_track = 3;
+      rx.restamp_cc[0] = rx.restamp_cc[1] = 1;
+    }
+    if (!st) st = dvbt2ll_tsmux_set_remux(mux, &rx);
+    if (st) { std::fprintf(stderr, "dvbt2ll_tx: mux: bad remap= / restamp-cc\n"); dvbt2ll_tsmux_destroy(mux); return nullptr; }
+  }
   FILE *out_f = std::tmpfile();
   if (!out_f) { std::fprintf(stderr, "dvbt2ll_tx: cannot open a temporary file: %s\n", std::strerror(errno)); dvbt2ll_tsmux_destroy(mux); return nullptr; }
   std::vector<uint8_t> out((size_t)per_call * 188);
@@ -869,13 +912,25 @@ FILE *run_mux(FILE *ts, const MuxOpt &m, int pid, int device) {
   std::memset(&pos, 0, sizeof(pos));
   const int64_t total = (int64_t)(in.size() / 188);
   int64_t used = 0, slots = 0, psi_packets = 0, in_free = 0, pcr = 0, nulls = 0, sync = 0;
+  dvbt2ll_tsmux_remux_pos rpos;
+  std::memset(&rpos, 0, sizeof(rpos));
+  int64_t remapped = 0, dropped = 0, cc_rewritten = 0, pcr_restamped = 0;
   while (!st && used < total) {
     // a call of per_call slots takes at most per_call packets, so it is given that window of the encapsulated TS
     const void *ptr[DVBT2LL_TSMUX_INPUTS] = {in.data() + (size_t)used * 188, psi.data()};
     const int64_t n_in[DVBT2LL_TSMUX_INPUTS] = {std::min(per_call, total - used), npsi};
     pos.next[0] = 0;
     dvbt2ll_tsmux_result res;
-    if ((st = dvbt2ll_tsmux_run_host(mux, ptr, n_in, &pos, out.data(), per_call, &res))) break;
+    dvbt2ll_tsmux_remux_result rres;
+    std::memset(&rres, 0, sizeof(rres));
+    if (remux) st = dvbt2ll_tsmux_run_host_remux(mux, ptr, n_in, &pos, &rpos, out.data(), per_call, &res, &rres);
+    else st = dvbt2ll_tsmux_run_host(mux, ptr, n_in, &pos, out.data(), per_call, &res);
+    if (st) break;
+    rpos = rres.resume;
+    remapped += rres.remapped;
+    dropped += rres.dropped;
+    cc_rewritten += rres.cc_rewritten;
+    pcr_restamped += rres.pcr_restamped;
     if (std::fwrite(out.data(), 188, (size_t)per_call, out_f) != (size_t)per_call) { st = -1; break; }
     pos = res.resume;
     used += res.consumed[0];
@@ -891,6 +946,9 @@ FILE *run_mux(FILE *ts, const MuxOpt &m, int pid, int device) {
   std::fprintf(stderr, "dvbt2ll_tx: mux: slots %lld, consumed %lld, psi_packets %lld, fill_in_free %lld, pcr_packets %lld, "
                "null_packets %lld, sync_errors %lld\n", (long long)slots, (long long)used, (long long)psi_packets,
                (long long)in_free, (long long)pcr, (long long)nulls, (long long)sync);
+  if (remux)
+    std::fprintf(stderr, "dvbt2ll_tx: remux: remapped %lld, dropped %lld, cc_rewritten %lld, pcr_restamped %lld\n",
+                 (long long)remapped, (long long)dropped, (long long)cc_rewritten, (long long)pcr_restamped);
   dvbt2ll_tsmux_destroy(mux);
   if (st) { std::fclose(out_f); return nullptr; }
   std::rewind(out_f);

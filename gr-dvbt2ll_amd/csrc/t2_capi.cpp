@@ -2616,6 +2616,13 @@ struct dvbt2ll_tsmux {
   hipEvent_t done = nullptr;     // the last run; a run on another stream waits for it (the counters are shared)
   hipStream_t last = nullptr;
   bool ran = false;
+  // the remux (dvbt2ll_tsmux_set_remux): its tables and scan scratch, the last run's start position
+  bool remux = false;
+  dvbt2ll_tsmux_remux x{};
+  TsremuxDev xdev;
+  DevBuf pid_map, slot_of, tiles, chunks, xres;
+  dvbt2ll_tsmux_remux_pos rstart{};
+  int64_t tpp = 0;               // the mux clock: p.ticks_per_period, or the remux's out_ticks_per_period
   ~dvbt2ll_tsmux() {
     if (done) { (void)hipSetDevice(ctx.device); (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
   }
@@ -2628,6 +2635,7 @@ extern "C" int dvbt2ll_tsmux_create(const dvbt2ll_tsmux_params *p, int device, d
   std::unique_ptr<dvbt2ll_tsmux> h(new (std::nothrow) dvbt2ll_tsmux());
   if (!h) return DVBT2LL_ENOMEM;
   h->p = *p;
+  h->tpp = p->ticks_per_period;
   int r = h->ctx.init(device);
   if (r) return r;
   tsmux_plan(*p, h->plan);
@@ -2675,21 +2683,120 @@ static int tsmux_run_args(const dvbt2ll_tsmux *h, const void *const *in, const i
   return DVBT2LL_OK;
 }
 
-extern "C" int dvbt2ll_tsmux_run_device(dvbt2ll_tsmux *h, const void *const *in_dev, const int64_t *n_in,
-                                        const dvbt2ll_tsmux_pos *start, void *out_dev, int64_t n_out, void *stream) {
+// rstart: the remux position of a handle with a remux, null on one without (each run call refuses the other kind)
+static int tsmux_run(dvbt2ll_tsmux *h, const void *const *in_dev, const int64_t *n_in, const dvbt2ll_tsmux_pos *start,
+                     const dvbt2ll_tsmux_remux_pos *rstart, void *out_dev, int64_t n_out, void *stream) {
   TsmuxRun r;
+  TsremuxRun y;
   int e = tsmux_run_args(h, in_dev, n_in, start, out_dev, n_out, r);
   if (e) return e;
+  if (h->remux != (rstart != nullptr)) return DVBT2LL_EINVAL;
+  if (rstart) {
+    for (int s = 0; s < DVBT2LL_TSMUX_TRACK; s++) {
+      if (rstart->cc[s] < 0 || rstart->cc[s] > (s < h->x.n_track ? 15 : 0)) return DVBT2LL_EINVAL;
+      y.cc[s / 16] |= (unsigned long long)rstart->cc[s] << (4 * (s % 16));
+    }
+    for (int i = 0; i < TSMUX_IN; i++) {
+      const int64_t per = h->x.in_period[i], tpp = h->x.in_ticks_per_period[i];
+      if (rstart->in_phase[i] < 0 || rstart->in_phase[i] > std::max<int64_t>(per, 1) - 1) return DVBT2LL_EINVAL;
+      if (rstart->in_ticks[i] < 0 || rstart->in_ticks[i] >= (per ? TSMUX_PCR_WRAP : 1)) return DVBT2LL_EINVAL;
+      // the input's clock stays inside 64 bits: (n_in / in_period + 1) x in_ticks_per_period <= 2^62, without the product
+      if (per && n_in[i] / per + 1 > ((int64_t)1 << 62) / tpp) return DVBT2LL_EINVAL;
+      y.in_phase[i] = (uint32_t)rstart->in_phase[i];
+      y.in_ticks[i] = (unsigned long long)rstart->in_ticks[i];
+    }
+  }
   HIP_TRY(hipSetDevice(h->ctx.device));
   hipStream_t st = stream ? (hipStream_t)stream : h->ctx.stream;
   if (h->ran && h->last != st) HIP_TRY(hipStreamWaitEvent(st, h->done, 0));
-  HIP_TRY(tsmux_launch(h->dev, r, st));
+  if (rstart) {
+    HIP_TRY(tsremux_launch(h->dev, h->xdev, r, y, st));
+    h->rstart = *rstart;
+  } else HIP_TRY(tsmux_launch(h->dev, r, st));
   HIP_TRY(hipEventRecord(h->done, st));
   h->start = *start;
   h->n_out = n_out;
   for (int i = 0; i < TSMUX_IN; i++) h->n_in[i] = i < h->p.n_inputs ? n_in[i] : 0;
   h->last = st;
   h->ran = true;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_tsmux_run_device(dvbt2ll_tsmux *h, const void *const *in_dev, const int64_t *n_in,
+                                        const dvbt2ll_tsmux_pos *start, void *out_dev, int64_t n_out, void *stream) {
+  return tsmux_run(h, in_dev, n_in, start, nullptr, out_dev, n_out, stream);
+}
+
+extern "C" int dvbt2ll_tsmux_run_device_remux(dvbt2ll_tsmux *h, const void *const *in_dev, const int64_t *n_in,
+                                              const dvbt2ll_tsmux_pos *start, const dvbt2ll_tsmux_remux_pos *rstart,
+                                              void *out_dev, int64_t n_out, void *stream) {
+  if (!rstart) return DVBT2LL_EINVAL;
+  return tsmux_run(h, in_dev, n_in, start, rstart, out_dev, n_out, stream);
+}
+
+extern "C" int dvbt2ll_tsmux_set_remux(dvbt2ll_tsmux *h, const dvbt2ll_tsmux_remux *x) {
+  if (!h || !x || h->ran || h->remux || !tsmux_remux_ok(h->p, *x)) return DVBT2LL_EINVAL;
+  HIP_TRY(hipSetDevice(h->ctx.device));
+  const int n = h->p.n_inputs;
+  std::vector<uint16_t> pid_map((size_t)TSMUX_IN * 8192);
+  for (size_t k = 0; k < pid_map.size(); k++) pid_map[k] = (uint16_t)(k & 8191);
+  for (int a = 0; a < x->n_map; a++)
+    pid_map[(size_t)x->map[a].input * 8192 + x->map[a].from_pid] = (uint16_t)(TSREMUX_ENTRY | x->map[a].to_pid);
+  std::vector<uint8_t> slot_of(8192, (uint8_t)TSREMUX_NO_SLOT);
+  for (int s = 0; s < x->n_track; s++) slot_of[x->track_pid[s]] = (uint8_t)s;
+  int r;
+  if ((r = upload(h->pid_map, pid_map)) || (r = upload(h->slot_of, slot_of))) return r;
+  const size_t ntiles = ((size_t)h->p.max_out_packets + TSREMUX_TILE - 1) / TSREMUX_TILE;
+  const size_t nchunks = (ntiles + TSREMUX_SCAN_TILES - 1) / TSREMUX_SCAN_TILES;
+  if (h->tiles.ensure(ntiles * TSREMUX_SLOTS) || h->chunks.ensure(nchunks * TSREMUX_SLOTS) ||
+      h->xres.ensure(TSREMUX_R_WORDS * 8))
+    return DVBT2LL_ENOMEM;
+  HIP_TRY(hipMemset(h->xres.p, 0, TSREMUX_R_WORDS * 8));
+  TsremuxDev &d = h->xdev;
+  d.pid_map = h->pid_map.as<uint16_t>();
+  d.slot_of = h->slot_of.as<uint8_t>();
+  d.tiles = h->tiles.as<uint8_t>();
+  d.chunks = h->chunks.as<uint8_t>();
+  d.res = h->xres.as<unsigned long long>();
+  for (int i = 0; i < n; i++) {
+    d.restamp_cc |= (uint32_t)x->restamp_cc[i] << i;
+    if (!x->in_period[i]) continue;
+    d.in_period[i] = (uint32_t)x->in_period[i];
+    d.in_tpp[i] = (unsigned long long)x->in_ticks_per_period[i];
+    d.in_q[i] = d.in_tpp[i] / d.in_period[i];
+    d.in_r[i] = (uint32_t)(d.in_tpp[i] % d.in_period[i]);
+  }
+  // the slot clock of a handle without a PCR PID, which no kernel of a plain handle reads
+  h->tpp = tsmux_remux_tpp(h->p, *x);
+  h->dev.tpp = (unsigned long long)h->tpp;
+  h->dev.tpp_q = h->dev.tpp / h->dev.period;
+  h->dev.tpp_r = (uint32_t)(h->dev.tpp % h->dev.period);
+  h->x = *x;
+  h->remux = true;
+  return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_tsmux_get_remux_result(dvbt2ll_tsmux *h, dvbt2ll_tsmux_remux_result *res) {
+  if (!h || !res || !h->remux) return DVBT2LL_EINVAL;
+  dvbt2ll_tsmux_result plain;
+  int e = dvbt2ll_tsmux_get_result(h, &plain);   // synchronises
+  if (e) return e;
+  uint64_t w[TSREMUX_R_WORDS];
+  HIP_TRY(hipMemcpy(w, h->xdev.res, sizeof w, hipMemcpyDeviceToHost));
+  memset(res, 0, sizeof *res);
+  res->remapped = (int64_t)w[TSREMUX_R_REMAPPED];
+  res->dropped = (int64_t)w[TSREMUX_R_DROPPED];
+  res->cc_rewritten = (int64_t)w[TSREMUX_R_CC_REWRITTEN];
+  res->pcr_restamped = (int64_t)w[TSREMUX_R_PCR];
+  for (int s = 0; s < h->x.n_track; s++) res->resume.cc[s] = (int)((h->rstart.cc[s] + w[TSREMUX_R_CC + s]) & 15);
+  for (int i = 0; i < h->p.n_inputs; i++) {
+    const int64_t per = h->x.in_period[i];
+    if (!per) continue;
+    const int64_t at = h->rstart.in_phase[i] + plain.consumed[i];
+    res->resume.in_phase[i] = (int)(at % per);
+    // at most 2^31 periods of less than 2^36 ticks, checked against 2^62 at the run
+    res->resume.in_ticks[i] = (h->rstart.in_ticks[i] + (at / per) * h->x.in_ticks_per_period[i]) % TSMUX_PCR_WRAP;
+  }
   return DVBT2LL_OK;
 }
 
@@ -2713,17 +2820,18 @@ extern "C" int dvbt2ll_tsmux_get_result(dvbt2ll_tsmux *h, dvbt2ll_tsmux_result *
   const int64_t at = h->start.phase + h->n_out;
   res->resume.phase = (int)(at % h->p.period);
   // the periods passed are at most 2^24 + 1 and ticks_per_period is below 2^36
-  res->resume.pcr_ticks = (h->start.pcr_ticks + (at / h->p.period) * h->p.ticks_per_period) % TSMUX_PCR_WRAP;
+  res->resume.pcr_ticks = (h->start.pcr_ticks + (at / h->p.period) * h->tpp) % TSMUX_PCR_WRAP;
   return DVBT2LL_OK;
 }
 
-extern "C" int dvbt2ll_tsmux_run_host(dvbt2ll_tsmux *h, const void *const *in, const int64_t *n_in,
-                                      const dvbt2ll_tsmux_pos *start, void *out, int64_t n_out,
-                                      dvbt2ll_tsmux_result *res) {
+static int tsmux_run_host(dvbt2ll_tsmux *h, const void *const *in, const int64_t *n_in, const dvbt2ll_tsmux_pos *start,
+                          const dvbt2ll_tsmux_remux_pos *rstart, void *out, int64_t n_out, dvbt2ll_tsmux_result *res,
+                          dvbt2ll_tsmux_remux_result *rres) {
   TsmuxRun r;
   if (!res) return DVBT2LL_EINVAL;
   int e = tsmux_run_args(h, in, n_in, start, out, n_out, r);
   if (e) return e;
+  if (h->remux != (rstart != nullptr)) return DVBT2LL_EINVAL;
   HIP_TRY(hipSetDevice(h->ctx.device));
   if (h->ran) HIP_TRY(hipEventSynchronize(h->done));
   hipStream_t st = h->ctx.stream;
@@ -2735,10 +2843,25 @@ extern "C" int dvbt2ll_tsmux_run_host(dvbt2ll_tsmux *h, const void *const *in, c
     dev_in[i] = h->in_tmp[i].p;
   }
   if (h->out_tmp.ensure((size_t)std::max<int64_t>(n_out, 1) * 188)) return DVBT2LL_ENOMEM;
-  if ((e = dvbt2ll_tsmux_run_device(h, dev_in, n_in, start, h->out_tmp.p, n_out, st))) return e;
+  if ((e = tsmux_run(h, dev_in, n_in, start, rstart, h->out_tmp.p, n_out, st))) return e;
   if ((e = dvbt2ll_tsmux_get_result(h, res))) return e;
+  if (rstart && (e = dvbt2ll_tsmux_get_remux_result(h, rres))) return e;
   if (n_out > 0) HIP_TRY(hipMemcpy(out, h->out_tmp.p, (size_t)n_out * 188, hipMemcpyDeviceToHost));
   return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_tsmux_run_host(dvbt2ll_tsmux *h, const void *const *in, const int64_t *n_in,
+                                      const dvbt2ll_tsmux_pos *start, void *out, int64_t n_out,
+                                      dvbt2ll_tsmux_result *res) {
+  return tsmux_run_host(h, in, n_in, start, nullptr, out, n_out, res, nullptr);
+}
+
+extern "C" int dvbt2ll_tsmux_run_host_remux(dvbt2ll_tsmux *h, const void *const *in, const int64_t *n_in,
+                                            const dvbt2ll_tsmux_pos *start, const dvbt2ll_tsmux_remux_pos *rstart,
+                                            void *out, int64_t n_out, dvbt2ll_tsmux_result *res,
+                                            dvbt2ll_tsmux_remux_result *rres) {
+  if (!rstart || !rres) return DVBT2LL_EINVAL;
+  return tsmux_run_host(h, in, n_in, start, rstart, out, n_out, res, rres);
 }
 
 extern "C" void dvbt2ll_tsmux_destroy(dvbt2ll_tsmux *h) { delete h; }

@@ -44,5 +44,44 @@ struct TsmuxRun {
 // one run on stream: the counters are zeroed, then one kernel; no host round trip
 hipError_t tsmux_launch(const TsmuxDev &d, const TsmuxRun &r, hipStream_t stream);
 
+// ---------------------------------------------------------------------------- remux (dvbt2ll_tsmux_*_remux)
+constexpr int TSREMUX_SLOTS = 64;               // DVBT2LL_TSMUX_TRACK: tracked PIDs
+constexpr uint32_t TSREMUX_TILE = TSMUX_PKTS;   // output packets per row of payload counts: one trip, one wave
+constexpr uint32_t TSREMUX_SCAN_TILES = 256;    // tiles one workgroup of the scan's first round covers; a call of more
+                                                // tiles has a non-zero base from the second round (the scan over chunks)
+constexpr uint32_t TSREMUX_MAX_CHUNKS = (1u << 24) / TSREMUX_TILE / TSREMUX_SCAN_TILES;   // 1024
+constexpr uint32_t TSREMUX_NO_SLOT = 0xFF;      // slot_of[pid] of a PID that is not tracked
+constexpr uint32_t TSREMUX_DROP = 0x1FFF;       // a map target: the packet leaves as the null packet
+constexpr uint32_t TSREMUX_ENTRY = 0x8000;      // pid_map: the value comes from a map entry
+
+// the device result of a remux run, 64-bit words; TSREMUX_R_CC + s: the payload packets restamped on slot s, mod 256
+enum : int { TSREMUX_R_REMAPPED = 0, TSREMUX_R_DROPPED, TSREMUX_R_CC_REWRITTEN, TSREMUX_R_PCR, TSREMUX_R_CC,
+             TSREMUX_R_WORDS = TSREMUX_R_CC + TSREMUX_SLOTS };
+
+struct TsremuxDev {
+  const uint16_t *pid_map = nullptr;  // TSMUX_IN x 8192: TSREMUX_ENTRY | to_pid where (input, PID) has a map entry, else the PID
+  const uint8_t *slot_of = nullptr;   // 8192: the tracked slot of an output PID, or TSREMUX_NO_SLOT
+  uint8_t *tiles = nullptr;           // a row of TSREMUX_SLOTS bytes per tile: the payload counts, then their exclusive
+                                      // prefix inside the tile's chunk (mod 256; a counter needs it mod 16)
+  uint8_t *chunks = nullptr;          // a row per chunk of TSREMUX_SCAN_TILES tiles: start cc + the chunks before it
+  unsigned long long *res = nullptr;  // TSREMUX_R_WORDS
+  uint32_t restamp_cc = 0;            // bit i: input i's packets on tracked PIDs get new counters
+  uint32_t in_period[TSMUX_IN] = {};  // 0: input i's PCRs pass unchanged
+  unsigned long long in_tpp[TSMUX_IN] = {};     // in_ticks_per_period = in_q x in_period + in_r, as TsmuxDev's tpp
+  unsigned long long in_q[TSMUX_IN] = {};
+  uint32_t in_r[TSMUX_IN] = {};
+};
+
+struct TsremuxRun {
+  unsigned long long cc[TSREMUX_SLOTS / 16] = {};   // the start counters, 4 bits each, slot s in word s / 16
+  uint32_t in_phase[TSMUX_IN] = {};
+  unsigned long long in_ticks[TSMUX_IN] = {};
+};
+
+// one remux run on stream: both sets of counters are zeroed, then classify, the two scan rounds and the emit kernel
+// (tsmux_mux's remux instantiation); no host round trip.  d is the handle's TsmuxDev with tpp holding the mux clock.
+hipError_t tsremux_launch(const TsmuxDev &d, const TsremuxDev &x, const TsmuxRun &r, const TsremuxRun &y,
+                          hipStream_t stream);
+
 }  // namespace t2
 #endif

@@ -54,6 +54,34 @@ void tsmux_plan(const dvbt2ll_tsmux_params &p, TsmuxPlan &plan) {
   }
 }
 
+bool tsmux_remux_ok(const dvbt2ll_tsmux_params &p, const dvbt2ll_tsmux_remux &x) {
+  if (x.n_map < 0 || x.n_map > DVBT2LL_TSMUX_MAP || x.n_track < 0 || x.n_track > DVBT2LL_TSMUX_TRACK) return false;
+  for (int a = 0; a < x.n_map; a++) {
+    const dvbt2ll_tsmux_map &m = x.map[a];
+    if (m.input < 0 || m.input >= p.n_inputs) return false;
+    if (m.from_pid < 0 || m.from_pid > 0x1FFF || m.to_pid < 0 || m.to_pid > 0x1FFF) return false;
+    if (p.pcr_pid >= 0 && m.to_pid == p.pcr_pid) return false;
+    for (int b = 0; b < a; b++)
+      if (x.map[b].input == m.input && x.map[b].from_pid == m.from_pid) return false;
+  }
+  for (int s = 0; s < x.n_track; s++) {
+    if (x.track_pid[s] < 0 || x.track_pid[s] > 0x1FFE) return false;
+    if (p.pcr_pid >= 0 && x.track_pid[s] == p.pcr_pid) return false;
+    for (int b = 0; b < s; b++)
+      if (x.track_pid[b] == x.track_pid[s]) return false;
+  }
+  for (int i = 0; i < DVBT2LL_TSMUX_INPUTS; i++) {
+    const bool used = i < p.n_inputs;
+    if (x.restamp_cc[i] != 0 && !(used && x.restamp_cc[i] == 1)) return false;
+    if (x.in_ticks_per_period[i] == 0 && x.in_period[i] == 0) continue;
+    if (!used || x.in_period[i] < 1 || x.in_period[i] > DVBT2LL_TSMUX_MAX_PERIOD) return false;
+    if (x.in_ticks_per_period[i] < 1 || x.in_ticks_per_period[i] >= ((int64_t)1 << 36)) return false;
+  }
+  if (x.out_ticks_per_period < 0 || x.out_ticks_per_period >= ((int64_t)1 << 36)) return false;
+  if (p.pcr_pid >= 0 && x.out_ticks_per_period != 0 && x.out_ticks_per_period != p.ticks_per_period) return false;
+  return true;
+}
+
 namespace {
 
 // CRC-32 of generator 0x04C11DB7, initial value 0xFFFFFFFF, no reflection, no final XOR (the MPE section's)
@@ -104,6 +132,10 @@ extern "C" int dvbt2ll_tsmux_schedule(const dvbt2ll_tsmux_params *p, uint8_t *ow
   tsmux_plan(*p, plan);
   memcpy(owner, plan.table.data(), plan.table.size());
   return DVBT2LL_OK;
+}
+
+extern "C" int dvbt2ll_tsmux_remux_check(const dvbt2ll_tsmux_params *p, const dvbt2ll_tsmux_remux *x) {
+  return p && x && tsmux_params_ok(*p) && tsmux_remux_ok(*p, *x) ? DVBT2LL_OK : DVBT2LL_EINVAL;
 }
 
 extern "C" int64_t dvbt2ll_tsmux_ticks_per_period(int period, int64_t ts_bits_per_second) {

@@ -24,6 +24,12 @@ struct TsmuxPlan {
 bool tsmux_params_ok(const dvbt2ll_tsmux_params &p);
 // the table and prefix counts of valid params
 void tsmux_plan(const dvbt2ll_tsmux_params &p, TsmuxPlan &plan);
+// a remux configuration for a handle of valid params (dvbt2ll_tsmux_remux_check)
+bool tsmux_remux_ok(const dvbt2ll_tsmux_params &p, const dvbt2ll_tsmux_remux &x);
+// the mux clock of a handle of p with remux x: ticks per period
+inline int64_t tsmux_remux_tpp(const dvbt2ll_tsmux_params &p, const dvbt2ll_tsmux_remux &x) {
+  return p.pcr_pid >= 0 ? p.ticks_per_period : x.out_ticks_per_period;
+}
 
 }  // namespace t2
 #endif

@@ -15,7 +15,7 @@ from .modeadapt import ModeAdapter, ModeAdaptPos, ModeAdaptResult  # noqa: F401
 from .ule import UleEncapsulator, UlePos, UleResult  # noqa: F401
 from .mpe import MpeEncapsulator, MpePos, MpeResult  # noqa: F401
 from .mpefec import MpeFecEncapsulator, MpeFecPos, MpeFecResult  # noqa: F401
-from .tsmux import TsMux, TsMuxPos, TsMuxResult, psi_build, ticks_per_period  # noqa: F401
+from .tsmux import TsMux, TsMuxPos, TsMuxResult, TsRemuxPos, TsRemuxResult, psi_build, ticks_per_period  # noqa: F401
 from .gse import GseEncapsulator, GsePos, GseResult  # noqa: F401
 from .configs import CONFIGS, T2Config, ts_packets, ts_for_frames, bbframe_span  # noqa: F401
 from .configs import MPLP_CONFIGS, MplpConfig, PlpConfig  # noqa: F401

@@ -187,6 +187,30 @@ class _TsMuxResult(ctypes.Structure):
                     "fill_in_free", "pcr_packets", "null_packets", "sync_errors")]
 
 
+TSMUX_MAP, TSMUX_TRACK = 64, 64      # DVBT2LL_TSMUX_MAP, DVBT2LL_TSMUX_TRACK
+
+
+class _TsMuxMap(ctypes.Structure):
+    _fields_ = [("input", ctypes.c_int), ("from_pid", ctypes.c_int), ("to_pid", ctypes.c_int)]
+
+
+class _TsMuxRemux(ctypes.Structure):
+    _fields_ = [("n_map", ctypes.c_int), ("map", _TsMuxMap * TSMUX_MAP), ("n_track", ctypes.c_int),
+                ("track_pid", ctypes.c_int * TSMUX_TRACK), ("restamp_cc", ctypes.c_int * TSMUX_INPUTS),
+                ("in_period", ctypes.c_int * TSMUX_INPUTS), ("in_ticks_per_period", ctypes.c_int64 * TSMUX_INPUTS),
+                ("out_ticks_per_period", ctypes.c_int64)]
+
+
+class _TsMuxRemuxPos(ctypes.Structure):
+    _fields_ = [("cc", ctypes.c_int * TSMUX_TRACK), ("in_phase", ctypes.c_int * TSMUX_INPUTS),
+                ("in_ticks", ctypes.c_int64 * TSMUX_INPUTS)]
+
+
+class _TsMuxRemuxResult(ctypes.Structure):
+    _fields_ = [("resume", _TsMuxRemuxPos)] + [(n, ctypes.c_int64) for n in (
+        "remapped", "dropped", "cc_rewritten", "pcr_restamped")]
+
+
 class _PsiStream(ctypes.Structure):
     _fields_ = [("stream_type", ctypes.c_int), ("pid", ctypes.c_int), ("descriptor_len", ctypes.c_int),
                 ("descriptors", ctypes.c_uint8 * PSI_DESCRIPTOR_BYTES)]
@@ -275,7 +299,8 @@ EXPORTS += ["dvbt2ll_ule_" + f for f in ("create", "run_device", "get_result", "
 EXPORTS += ["dvbt2ll_mpe_" + f for f in ("create", "run_device", "get_result", "run_host", "destroy")]
 EXPORTS += ["dvbt2ll_mpefec_" + f for f in ("create", "run_device", "get_result", "run_host", "destroy")]
 EXPORTS += ["dvbt2ll_tsmux_" + f for f in ("schedule", "ticks_per_period", "create", "run_device", "get_result",
-                                           "run_host", "destroy")]
+                                           "run_host", "destroy", "remux_check", "set_remux", "run_device_remux",
+                                           "get_remux_result", "run_host_remux")]
 EXPORTS += ["dvbt2ll_psi_build"]
 EXPORTS += ["dvbt2ll_chain_" + f for f in ("create", "get_info", "run_device", "run_streams", "run_host", "set_output", "set_slots", "set_graph", "set_timing",
                                            "get_timing", "debug_codewords", "debug_cell_pairs", "debug_cells",
@@ -414,6 +439,14 @@ def lib():
     L.dvbt2ll_tsmux_run_host.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(_TsMuxPos), vp,
                                          i64, ctypes.POINTER(_TsMuxResult)]
     L.dvbt2ll_tsmux_destroy.argtypes = [vp]
+    L.dvbt2ll_tsmux_remux_check.argtypes = [ctypes.POINTER(_TsMuxParams), ctypes.POINTER(_TsMuxRemux)]
+    L.dvbt2ll_tsmux_set_remux.argtypes = [vp, ctypes.POINTER(_TsMuxRemux)]
+    L.dvbt2ll_tsmux_run_device_remux.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(_TsMuxPos),
+                                                 ctypes.POINTER(_TsMuxRemuxPos), vp, i64, vp]
+    L.dvbt2ll_tsmux_get_remux_result.argtypes = [vp, ctypes.POINTER(_TsMuxRemuxResult)]
+    L.dvbt2ll_tsmux_run_host_remux.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(_TsMuxPos),
+                                               ctypes.POINTER(_TsMuxRemuxPos), vp, i64, ctypes.POINTER(_TsMuxResult),
+                                               ctypes.POINTER(_TsMuxRemuxResult)]
     L.dvbt2ll_tsmux_destroy.restype = None
     L.dvbt2ll_psi_build.argtypes = [ctypes.POINTER(_PsiParams), vp, i64]
     L.dvbt2ll_psi_build.restype = i64

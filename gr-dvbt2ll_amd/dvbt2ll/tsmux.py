@@ -20,9 +20,10 @@ from typing import NamedTuple
 import numpy as np
 
 from ._lib import (lib, check, DVBT2Error, _TsMuxParams, _TsMuxPos, _TsMuxResult, _PsiParams, TSMUX_INPUTS,
-                   PSI_DESCRIPTOR_BYTES)
+                   PSI_DESCRIPTOR_BYTES, _TsMuxRemux, _TsMuxRemuxPos, _TsMuxRemuxResult, TSMUX_MAP, TSMUX_TRACK)
 
 COUNTERS = ("fill_in_free", "pcr_packets", "null_packets", "sync_errors")
+REMUX_COUNTERS = ("remapped", "dropped", "cc_rewritten", "pcr_restamped")
 PCR_WRAP = (1 << 33) * 300
 
 
@@ -34,6 +35,22 @@ class TsMuxPos(NamedTuple):
     next: tuple = (0,) * TSMUX_INPUTS
 
 
+class TsRemuxPos(NamedTuple):
+    """a remux position: cc[s], the counter the next payload packet restamped on tracked PID s takes; in_phase[i] and
+    in_ticks[i], where input i's next packet lies in the input's own period and the input's 27 MHz clock at the start
+    of that period"""
+    cc: tuple = (0,) * TSMUX_TRACK
+    in_phase: tuple = (0,) * TSMUX_INPUTS
+    in_ticks: tuple = (0,) * TSMUX_INPUTS
+
+
+@dataclass
+class TsRemuxResult:
+    """one call's remux result: resume (TsRemuxPos); counters (dict: remapped, dropped, cc_rewritten, pcr_restamped)"""
+    resume: TsRemuxPos
+    counters: dict
+
+
 @dataclass
 class TsMuxResult:
     """one call's result: resume (TsMuxPos); counters (dict: consumed and dry_slots are tuples per input); ts (uint8
@@ -41,6 +58,7 @@ class TsMuxResult:
     resume: TsMuxPos
     counters: dict
     ts: np.ndarray = None
+    remux: TsRemuxResult = None
 
 
 def ticks_per_period(period, ts_bits_per_second):
@@ -56,6 +74,37 @@ def _pos(start, n):
     pos.phase, pos.pcr_ticks = int(start[0]), int(start[1])
     for i, v in enumerate(list(start[2])[:n]):
         pos.next[i] = int(v)
+    return pos
+
+
+def _padded(v, n):
+    v = [int(x) for x in v]
+    return v + [0] * (n - len(v))
+
+
+def remux_params(map=(), track_pid=(), restamp_cc=(), in_period=(), in_ticks_per_period=(), out_ticks_per_period=0):
+    """the dvbt2ll_tsmux_remux of: map, (input, from_pid, to_pid) triples (to_pid 0x1FFF drops); track_pid, the output
+    PIDs whose continuity counters are kept; restamp_cc, 0 / 1 per input; in_period / in_ticks_per_period per input (0:
+    its PCRs pass unchanged); out_ticks_per_period, the mux clock of a handle without a PCR PID"""
+    x = _TsMuxRemux()
+    if len(map) > TSMUX_MAP or len(track_pid) > TSMUX_TRACK:
+        raise ValueError("at most %d map entries and %d tracked PIDs" % (TSMUX_MAP, TSMUX_TRACK))
+    x.n_map, x.n_track = len(map), len(track_pid)
+    for a, (i, f, t) in enumerate(map):
+        x.map[a].input, x.map[a].from_pid, x.map[a].to_pid = int(i), int(f), int(t)
+    x.track_pid[:len(track_pid)] = [int(v) for v in track_pid]
+    x.restamp_cc[:] = _padded(restamp_cc, TSMUX_INPUTS)
+    x.in_period[:] = _padded(in_period, TSMUX_INPUTS)
+    x.in_ticks_per_period[:] = _padded(in_ticks_per_period, TSMUX_INPUTS)
+    x.out_ticks_per_period = int(out_ticks_per_period)
+    return x
+
+
+def _rpos(rstart):
+    pos = _TsMuxRemuxPos()
+    pos.cc[:] = _padded(rstart[0], TSMUX_TRACK)
+    pos.in_phase[:] = _padded(rstart[1], TSMUX_INPUTS)
+    pos.in_ticks[:] = _padded(rstart[2], TSMUX_INPUTS)
     return pos
 
 
@@ -131,6 +180,49 @@ class TsMux:
                                            int(n_out), ctypes.byref(raw)), "tsmux run host")
         res = self._result(raw)
         res.ts = out[:int(n_out) * 188]
+        return res
+
+    # ------------------------------------------------------------------ remux (dvbt2ll_tsmux_*_remux)
+    def set_remux(self, map=(), track_pid=(), restamp_cc=(), in_period=(), in_ticks_per_period=(),
+                  out_ticks_per_period=0):
+        """once, before the first run: PID remapping, continuity restamping on the tracked PIDs and PCR restamping (see
+        remux_params).  The handle is then run with run_device_remux / run_host_remux; the plain calls refuse it"""
+        x = remux_params(map, track_pid, restamp_cc, in_period, in_ticks_per_period, out_ticks_per_period)
+        check(lib().dvbt2ll_tsmux_set_remux(self._h, ctypes.byref(x)), "tsmux set_remux")
+
+    def run_device_remux(self, in_ptrs, n_in, out_ptr, n_out, start=TsMuxPos(), rstart=TsRemuxPos(), stream=0):
+        """run_device on a handle with a remux, from the two positions"""
+        a, c = self._args(in_ptrs, n_in)
+        pos, rpos = _pos(start, self.n_inputs), _rpos(rstart)
+        check(lib().dvbt2ll_tsmux_run_device_remux(self._h, a, c, ctypes.byref(pos), ctypes.byref(rpos),
+                                                   ctypes.c_void_p(out_ptr), int(n_out),
+                                                   ctypes.c_void_p(stream or None)), "tsmux run remux")
+
+    @staticmethod
+    def _remux_result(raw):
+        pos = TsRemuxPos(tuple(int(v) for v in raw.resume.cc), tuple(int(v) for v in raw.resume.in_phase),
+                         tuple(int(v) for v in raw.resume.in_ticks))
+        return TsRemuxResult(pos, {k: int(getattr(raw, k)) for k in REMUX_COUNTERS})
+
+    def remux_result(self):
+        """synchronises with the last run: its TsRemuxResult (result() returns the multiplexer's own)"""
+        raw = _TsMuxRemuxResult()
+        check(lib().dvbt2ll_tsmux_get_remux_result(self._h, ctypes.byref(raw)), "tsmux remux result")
+        return self._remux_result(raw)
+
+    def run_host_remux(self, inputs, n_out, start=TsMuxPos(), rstart=TsRemuxPos()):
+        """host convenience (dvbt2ll_tsmux_run_host_remux): a TsMuxResult with ts and remux filled in"""
+        arrs = [np.ascontiguousarray(x, np.uint8).reshape(-1) for x in inputs]
+        a, c = self._args([x.ctypes.data if len(x) else 0 for x in arrs], [len(x) // 188 for x in arrs])
+        out = np.zeros(max(1, int(n_out)) * 188, np.uint8)
+        raw, rraw = _TsMuxResult(), _TsMuxRemuxResult()
+        pos, rpos = _pos(start, self.n_inputs), _rpos(rstart)
+        check(lib().dvbt2ll_tsmux_run_host_remux(self._h, a, c, ctypes.byref(pos), ctypes.byref(rpos),
+                                                 out.ctypes.data_as(ctypes.c_void_p), int(n_out), ctypes.byref(raw),
+                                                 ctypes.byref(rraw)), "tsmux run host remux")
+        res = self._result(raw)
+        res.ts = out[:int(n_out) * 188]
+        res.remux = self._remux_result(rraw)
         return res
 
     def __del__(self):

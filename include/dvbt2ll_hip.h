@@ -916,9 +916,9 @@ void dvbt2ll_mpefec_destroy(dvbt2ll_mpefec *h);
  * find its way in, and what the mode adapter then splits over the PLPs by PID.  A handle of its own beside the chain:
  * it holds the schedule tables and the last run's counters, no stream state.  Which input a slot belongs to is a fixed
  * periodic schedule, so every output packet is resolved on its own: no scan.  An input packet's bytes are never
- * altered.  Not built: PCR restamping of inputs that carry their own PCR, continuity restamping, per-PID remapping,
- * SDT / NIT / INT, section versions changing inside a carousel, GNU Radio adapters and distributed variants.  The
- * reference has no multiplexer, so all of this is PARITY UNPINNED, pinned by tests/tsmux_ref.py's sequential
+ * altered unless the handle has a remux (the next block: per-PID remapping, continuity and PCR restamping).  Not
+ * built: SDT / NIT / INT, section versions changing inside a carousel, GNU Radio adapters and distributed variants.
+ * The reference has no multiplexer, so all of this is PARITY UNPINNED, pinned by tests/tsmux_ref.py's sequential
  * restatement and its TS checker.
  *
  * schedule   the owners are the inputs 0 .. n - 1, the PCR generator (owner n, weight pcr_weight) and "null" (owner
@@ -1004,6 +1004,108 @@ int dvbt2ll_tsmux_get_result(dvbt2ll_tsmux *h, dvbt2ll_tsmux_result *res);
 int dvbt2ll_tsmux_run_host(dvbt2ll_tsmux *h, const void *const *in, const int64_t *n_in,
                            const dvbt2ll_tsmux_pos *start, void *out, int64_t n_out, dvbt2ll_tsmux_result *res);
 void dvbt2ll_tsmux_destroy(dvbt2ll_tsmux *h);
+
+/* ---------------------------------------------------------------------------
+ * TS multiplexer, remux: per-PID remapping, continuity restamping and PCR restamping, what lets the multiplexer take
+ * inputs it did not make: a recorded programme with its own PCR, a clip or carousel whose packet count per PID is no
+ * multiple of 16, an input that runs dry and goes on later, two inputs on one PID.  A configuration set once on a
+ * handle (dvbt2ll_tsmux_set_remux); the handle is then run with the *_remux calls, which take and return a second
+ * position beside dvbt2ll_tsmux_pos, and the plain run calls refuse it (DVBT2LL_EINVAL), so that nobody loses the
+ * continuity state by accident.  A handle on which set_remux was never called launches the plain kernel and writes
+ * the plain bytes.  Schedule, position, run, result and bounds of the block above hold unchanged; this block adds
+ * what happens to an input packet after it is resolved.  PARITY UNPINNED as the multiplexer is: pinned by
+ * tests/tsremux_ref.py's sequential restatement and its independent checker.
+ *
+ * order      per output packet: resolved as above.  A bad-sync packet becomes a null packet and nothing below applies
+ *            to it.  Then the remap, then the continuity restamp, then the PCR restamp.  Generated PCR packets and
+ *            null packets are not touched.
+ * remap      n_map entries {input, from_pid, to_pid}: a packet of that input with PID from_pid leaves with to_pid
+ *            (the other 3 bits of its byte 1 stay) and is counted in remapped.  to_pid 0x1FFF drops it: the packet is
+ *            consumed, counted in dropped (not in remapped) and in null_packets, and sent as the null packet 47 1F FF
+ *            10, 184 x FF, as a bad-sync packet is; nothing below applies to it.  Packets without an entry keep their
+ *            PID.  A pair (input, from_pid) may appear once.  No to_pid may be the handle's pcr_pid: that PID carries
+ *            nothing else.
+ * continuity n_track distinct output PIDs track_pid[s], none of them 0x1FFF or the handle's pcr_pid; s is the PID's
+ *            slot.  A packet is restamped on slot s when its input has restamp_cc set and its PID after the remap is
+ *            track_pid[s].  k(m) is the number of output packets before m in this call that were restamped on s and
+ *            carry a payload (adaptation_field_control & 1).  A restamped packet with a payload takes the counter
+ *            (cc[s] + k(m)) & 15, one without takes (cc[s] + k(m) - 1) & 15, the last payload packet's (13818-1
+ *            2.4.3.3).  Packets of an input with restamp_cc 0 are left alone and not counted, whatever their PID.
+ *            cc_rewritten counts the packets whose counter left different from how it came.
+ * PCR        for a packet of an input i with in_ticks_per_period[i] > 0 whose adaptation field is present
+ *            (adaptation_field_control & 2), at least 7 bytes long (byte 4 >= 7) and has PCR_flag (byte 5 & 0x10):
+ *            input i's in_period[i] packets last in_ticks_per_period[i] ticks, the formulation of period and
+ *            ticks_per_period.  j is the packet's rank among its input's packets in this call: r_i(m), or the claim
+ *            rank c(m) for the fill input; it is not reduced mod n_in[i] for a loop input.  in_phase[i] + j = dq
+ *            in_period[i] + r with 0 <= r < in_period[i]; T_in = in_ticks[i] + dq in_ticks_per_period[i] + floor(r
+ *            in_ticks_per_period[i] / in_period[i]); T_out is the slot's clock T of the block above, from the handle's
+ *            ticks_per_period or, on a handle without a PCR PID, from out_ticks_per_period; PCR_in = 300 base +
+ *            extension as found in bytes 6 .. 11; PCR_out = (PCR_in + T_out - T_in) mod W, written back as base, six 1
+ *            bits and extension, and the packet is counted in pcr_restamped.  OPCR, PTS and DTS are untouched.
+ *            Precondition: the correction keeps a programme clock right only if the caller gives the input slots at
+ *            its own long-term rate; pacing an input by its own clock is not built.  All arithmetic is 64-bit, as the
+ *            generator's: a run with (n_in[i] / in_period[i] + 1) x in_ticks_per_period[i] above 2^62 is refused.
+ * position   {cc[64], in_phase[8], in_ticks[8]}: cc[s], 0 .. 15, the counter the next payload packet restamped on
+ *            slot s takes (0 from n_track on); in_phase[i], 0 .. in_period[i] - 1, of input i's next packet; in_ticks[i],
+ *            0 .. W - 1, input i's clock at the start of the input period holding that packet.  Both are 0 for an input
+ *            whose in_ticks_per_period is 0.
+ * result     resume: cc[s] advanced by k(n_out), mod 16; in_phase[i] advanced by consumed[i] mod in_period[i];
+ *            in_ticks[i] advanced by ((in_phase[i] + consumed[i]) / in_period[i]) in_ticks_per_period[i], mod W.  The
+ *            multiplexer's own resume position is dvbt2ll_tsmux_result's; on a handle without a PCR PID its pcr_ticks
+ *            advances by out_ticks_per_period per period.  Chained calls at any split of n_out, each started from the
+ *            previous call's two resume positions, give the single call's bytes and summed counters.
+ * Not built: recognising duplicate packets (13818-1 allows one repeat of a packet; a repeat counts as a new packet
+ * here), setting discontinuity_indicator (it is left as it came), pacing an input by its own clock, more than 64 map
+ * entries or tracked PIDs, a PID shared with the PCR generator, SDT / NIT / INT, GNU Radio adapters and distributed
+ * variants.
+ * ------------------------------------------------------------------------- */
+#define DVBT2LL_TSMUX_MAP 64
+#define DVBT2LL_TSMUX_TRACK 64
+typedef struct {
+  int input;                             /* 0 .. n_inputs - 1 */
+  int from_pid, to_pid;                  /* 0 .. 0x1FFF; to_pid 0x1FFF: dropped */
+} dvbt2ll_tsmux_map;
+typedef struct {
+  int n_map;                             /* 0 .. 64 */
+  dvbt2ll_tsmux_map map[DVBT2LL_TSMUX_MAP];
+  int n_track;                           /* 0 .. 64 */
+  int track_pid[DVBT2LL_TSMUX_TRACK];    /* distinct, 0 .. 0x1FFE, not the handle's pcr_pid */
+  int restamp_cc[DVBT2LL_TSMUX_INPUTS];  /* 0 / 1 */
+  int in_period[DVBT2LL_TSMUX_INPUTS];   /* 1 .. 65536; 0 with in_ticks_per_period 0 */
+  int64_t in_ticks_per_period[DVBT2LL_TSMUX_INPUTS];   /* 1 .. 2^36 - 1; 0 (with in_period 0): the PCRs pass unchanged */
+  int64_t out_ticks_per_period;          /* the mux clock of a handle without a PCR PID, 0 .. 2^36 - 1; with one: 0 or
+                                            the handle's ticks_per_period */
+} dvbt2ll_tsmux_remux;
+typedef struct {
+  int cc[DVBT2LL_TSMUX_TRACK];           /* 0 .. 15 */
+  int in_phase[DVBT2LL_TSMUX_INPUTS];    /* 0 .. in_period[i] - 1 */
+  int64_t in_ticks[DVBT2LL_TSMUX_INPUTS];/* 0 .. 2^33 x 300 - 1 */
+} dvbt2ll_tsmux_remux_pos;
+typedef struct {
+  dvbt2ll_tsmux_remux_pos resume;
+  int64_t remapped, dropped, cc_rewritten, pcr_restamped;
+} dvbt2ll_tsmux_remux_result;
+/* host only, no GPU: 0, or DVBT2LL_EINVAL for a null pointer, params dvbt2ll_tsmux_schedule refuses, n_map or n_track
+ * outside 0 .. 64, an entry's input outside 0 .. n_inputs - 1 or a PID outside its range, a pair (input, from_pid)
+ * that appears twice, a tracked PID that repeats, a to_pid or tracked PID equal to pcr_pid, restamp_cc other than 0 / 1,
+ * in_period / in_ticks_per_period out of range or only one of them 0, out_ticks_per_period out of range or, on a handle
+ * with a PCR PID, neither 0 nor its ticks_per_period.  Entries of inputs from n_inputs on must be 0. */
+int dvbt2ll_tsmux_remux_check(const dvbt2ll_tsmux_params *p, const dvbt2ll_tsmux_remux *x);
+/* once per handle, before its first run: DVBT2LL_EINVAL as dvbt2ll_tsmux_remux_check, after a run, or a second time */
+int dvbt2ll_tsmux_set_remux(dvbt2ll_tsmux *h, const dvbt2ll_tsmux_remux *x);
+/* as dvbt2ll_tsmux_run_device, with the remux position.  DVBT2LL_EINVAL, nothing launched: as there, a handle without
+ * a remux, a null rstart, cc[s] outside 0 .. 15 (or not 0 from n_track on), in_phase[i] outside 0 .. in_period[i] - 1
+ * or in_ticks[i] outside [0, 2^33 x 300) (or not 0 where in_ticks_per_period[i] is 0), (n_in[i] / in_period[i] + 1) x
+ * in_ticks_per_period[i] above 2^62 */
+int dvbt2ll_tsmux_run_device_remux(dvbt2ll_tsmux *h, const void *const *in_dev, const int64_t *n_in,
+                                   const dvbt2ll_tsmux_pos *start, const dvbt2ll_tsmux_remux_pos *rstart,
+                                   void *out_dev, int64_t n_out, void *stream);
+/* synchronises with the last run and returns its remux result (dvbt2ll_tsmux_get_result returns the other) */
+int dvbt2ll_tsmux_get_remux_result(dvbt2ll_tsmux *h, dvbt2ll_tsmux_remux_result *res);
+/* host buffers, synchronous, as dvbt2ll_tsmux_run_host */
+int dvbt2ll_tsmux_run_host_remux(dvbt2ll_tsmux *h, const void *const *in, const int64_t *n_in,
+                                 const dvbt2ll_tsmux_pos *start, const dvbt2ll_tsmux_remux_pos *rstart, void *out,
+                                 int64_t n_out, dvbt2ll_tsmux_result *res, dvbt2ll_tsmux_remux_result *rres);
 
 /* ---------------------------------------------------------------------------
  * PSI builder (host only): a PAT and one PMT per programme (ISO/IEC 13818-1 2.4.4) as a carousel of TS packets for a
