@@ -23,13 +23,14 @@
 #include "gse_kernels.h"
 
 #include <algorithm>
-#include <type_traits>
+
+#include "crc32_mpeg2.h"
+#include "host_util.h"
 
 namespace t2 {
 
 namespace {
 
-constexpr uint32_t GSE_POLY = 0x04C11DB7u;
 enum : uint32_t { G_LEN = 0xFFFFu, G_SKIP_TYPE = 1u << 30, G_SKIP_LEN = 1u << 31 };
 enum : int { C_T = 0, C_U = 1, C_S = 2, C_NFRAG = 3 };   // d.ctl
 constexpr uint32_t ST_MASK = (1u << GSE_STATE_BITS) - 1;
@@ -172,36 +173,6 @@ __global__ __launch_bounds__(256) void gse_walk(GseDev d, uint32_t N) {
 }
 
 // ------------------------------------------------------------------------------------------ CRC-32
-__device__ inline uint32_t gf_mul(uint32_t a, uint32_t b) {   // a(x) b(x) mod G, bit 31 = x^31
-  uint32_t r = 0;
-  for (int i = 31; i >= 0; i--) {
-    r = (r << 1) ^ ((r >> 31) ? GSE_POLY : 0u);
-    if ((b >> i) & 1) r ^= a;
-  }
-  return r;
-}
-
-__device__ inline uint32_t crc_byte(uint32_t crc, uint32_t b, const uint32_t *tab) {
-  return (crc << 8) ^ tab[(crc >> 24) ^ b];
-}
-
-// n bytes at p, all inside one PDU: bytes up to a 4-byte boundary, aligned words, the rest
-__device__ inline uint32_t crc_run(uint32_t crc, const uint8_t *p, uint32_t n, const uint32_t *tab) {
-  while (n && ((uintptr_t)p & 3)) {
-    crc = crc_byte(crc, *p++, tab);
-    n--;
-  }
-  for (; n >= 4; n -= 4, p += 4) {
-    const uint32_t w = *(const uint32_t *)p;
-    crc = crc_byte(crc, w & 255, tab);
-    crc = crc_byte(crc, (w >> 8) & 255, tab);
-    crc = crc_byte(crc, (w >> 16) & 255, tab);
-    crc = crc_byte(crc, w >> 24, tab);
-  }
-  for (; n; n--) crc = crc_byte(crc, *p++, tab);
-  return crc;
-}
-
 // byte k < 4 + L of what the CRC covers before the PDU: Total Length, Protocol Type, Label
 __device__ inline uint32_t gse_covered_byte(const GseDev &d, uint32_t len, uint32_t type, uint32_t k) {
   const uint32_t total = 2 + d.L + len;
@@ -216,8 +187,8 @@ __device__ inline uint32_t gse_covered_byte(const GseDev &d, uint32_t len, uint3
 __device__ inline uint32_t crc_span(const GseDev &d, uint32_t crc, uint32_t len, uint32_t type, const uint8_t *pdu,
                                     uint32_t lo, uint32_t hi, const uint32_t *tab) {
   const uint32_t hl = 4 + d.L;
-  for (; lo < hi && lo < hl; lo++) crc = crc_byte(crc, gse_covered_byte(d, len, type, lo), tab);
-  if (lo < hi) crc = crc_run(crc, pdu + (lo - hl), hi - lo, tab);
+  for (; lo < hi && lo < hl; lo++) crc = crc32m_byte(crc, gse_covered_byte(d, len, type, lo), tab);
+  if (lo < hi) crc = crc32m_run(crc, pdu + (lo - hl), hi - lo, tab);
   return crc;
 }
 
@@ -235,20 +206,12 @@ __global__ __launch_bounds__(256) void gse_crc(GseDev d, GseRun r) {
     if (j >= r.n) continue;
     const uint32_t len = d.len[j] & G_LEN, tj = d.typ[j], oj = r.off[r.i0 + j];
     if (!len) continue;
-    // the T bytes are padded in front to 64 chunks of c bytes: leading zeros leave a zero register unchanged, so every
-    // lane's chunk has the same length and the tree multiplies by x^(8 c 2^m) at level m; the initial 0xFFFFFFFF is
-    // added as 0xFFFFFFFF x^(8 T)
-    const uint32_t T = 4 + d.L + len, c = (T + 63) >> 6, pad = 64 * c - T;
-    int lo = (int)(lane * c) - (int)pad, hi = lo + (int)c;
-    if (lo < 0) lo = 0;
+    const uint32_t T = 4 + d.L + len;
+    int lo, hi;
+    const uint32_t c = crc32m_wave_chunk(lane, T, lo, hi);
     uint32_t crc = 0;
     if (hi > lo) crc = crc_span(d, 0, len, tj, r.pdu + oj, (uint32_t)lo, (uint32_t)hi, tab);
-    for (int lv = 0; lv < 6; lv++) {
-      const uint32_t other = __shfl_xor(crc, 1 << lv);
-      const bool right = (lane >> lv) & 1;
-      crc = gf_mul(right ? other : crc, xp[c << lv]) ^ (right ? crc : other);
-    }
-    crc ^= gf_mul(0xFFFFFFFFu, xp[T]);
+    crc = crc32m_wave_join(crc, lane, c, T, xp);
     if (lane == 0) d.crc[j] = crc;
   }
 }
@@ -537,26 +500,11 @@ __global__ __launch_bounds__(256) void gse_count(GseDev d, GseRun r) {
 }  // namespace
 
 void gse_host_tables(uint32_t *tab) {
-  for (uint32_t v = 0; v < 256; v++) {
-    uint32_t c = v << 24;
-    for (int i = 0; i < 8; i++) c = (c << 1) ^ ((c >> 31) ? GSE_POLY : 0u);
-    tab[v] = c;
-  }
-  uint32_t p = 1;   // x^(8 n) mod G
-  for (int n = 0; n + 256 < GSE_TAB_WORDS; n++) {
-    tab[256 + n] = p;
-    p = (p << 8) ^ tab[p >> 24];
-  }
+  crc32m_host_tables(tab, GSE_TAB_WORDS - 256);
 }
 
 size_t gse_layout(GseDev &d, void *base) {
-  size_t at = 0;
-  auto take = [&](auto *&ptr, size_t count) {
-    using E = std::remove_reference_t<decltype(*ptr)>;
-    at = (at + 255) & ~(size_t)255;
-    ptr = base ? (E *)((char *)base + at) : nullptr;
-    at += count * sizeof(E);
-  };
+  LayoutTaker take{base};
   const size_t n = std::max<uint32_t>(d.max_pdus, 1), nt = tiles_of(d.max_pdus);
   take(d.res, GSE_R_WORDS + 2);
   d.ctl = base ? (uint32_t *)(d.res + GSE_R_WORDS) : nullptr;
@@ -570,7 +518,7 @@ size_t gse_layout(GseDev &d, void *base) {
   take(d.ent_u, nt);
   take(d.ent_fr, nt);
   take(d.tab, GSE_TAB_WORDS);
-  return at;
+  return take.at;
 }
 
 uint64_t gse_frame_estimate(const GseDev &d, uint64_t pdu_len, uint64_t n) {

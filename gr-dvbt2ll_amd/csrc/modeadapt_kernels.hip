@@ -21,105 +21,42 @@
 
 #include <algorithm>
 
+#include "dev_scan.h"
+#include "host_util.h"
+
 namespace t2 {
+
+// found by the scan templates through argument-dependent lookup
+__host__ __device__ inline MaMax operator+(const MaMax &a, const MaMax &b) { return MaMax{a.v > b.v ? a.v : b.v}; }
 
 namespace {
 
 enum : uint32_t { MA_SEL = 1, MA_SYNC_ERR = 2 };
 enum : uint32_t { MA_TX = 0x100 };
-constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 4, SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
 constexpr uint32_t PKT_MASK = 0xFFFFFFu;   // a run has fewer than 2^31 / 188 < 2^24 packets
 
-__host__ __device__ inline MaMax operator+(const MaMax &a, const MaMax &b) { return MaMax{a.v > b.v ? a.v : b.v}; }
-
 // ------------------------------------------------------------------------------------------ device-wide scan
-// (the three-launch structure of t2mi_kernels.hip: tile sums of 1024, one workgroup over the sums, apply)
-// exclusive scan of 256 per-thread values through LDS (2 x 256 entries); total = their sum
 template <class T>
-__device__ T block_exclusive(T v, T *lds, T &total) {
-  const int t = threadIdx.x;
-  T *a = lds, *b = lds + SCAN_THREADS;
-  a[t] = v;
-  __syncthreads();
-  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-    T x = a[t];
-    if (t >= d) x = a[t - d] + x;
-    b[t] = x;
-    __syncthreads();
-    T *s = a; a = b; b = s;
-  }
-  total = a[SCAN_THREADS - 1];
-  T ex = t ? a[t - 1] : T{};
-  __syncthreads();
-  return ex;
-}
-
-template <class T>
-__global__ __launch_bounds__(SCAN_THREADS) void modeadapt_scan_reduce(const T *in, T *tile, uint32_t n) {
+__global__ __launch_bounds__(SCAN_THREADS) void modeadapt_scan_reduce(const T *in, T *tile, uint32_t n,
+                                                                      const uint32_t *n_dev) {
   __shared__ T lds[SCAN_THREADS];
-  const uint32_t i0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  T s{};
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++) {
-    T x{};
-    if (i0 + q < n) x = in[i0 + q];
-    s = s + x;
-  }
-  lds[threadIdx.x] = s;
-  __syncthreads();
-  for (int dd = SCAN_THREADS / 2; dd > 0; dd >>= 1) {
-    if ((int)threadIdx.x < dd) lds[threadIdx.x] = lds[threadIdx.x] + lds[threadIdx.x + dd];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) tile[blockIdx.x] = lds[0];
+  scan_reduce_body(in, tile, n, n_dev, lds);
 }
-
-// one workgroup: tile sums -> exclusive tile offsets in place, the grand total to tile[ntiles]
 template <class T>
 __global__ __launch_bounds__(SCAN_THREADS) void modeadapt_scan_tiles(T *tile, uint32_t ntiles) {
   __shared__ T lds[2 * SCAN_THREADS];
-  T carry{};
-  for (uint32_t b = 0; b < ntiles; b += SCAN_THREADS) {
-    const uint32_t i = b + threadIdx.x;
-    T v = i < ntiles ? tile[i] : T{};
-    T total;
-    T ex = block_exclusive(v, lds, total);
-    if (i < ntiles) tile[i] = carry + ex;
-    carry = carry + total;
-  }
-  if (threadIdx.x == 0) tile[ntiles] = carry;
+  scan_tiles_body(tile, ntiles, lds);
 }
-
 template <class T>
-__global__ __launch_bounds__(SCAN_THREADS) void modeadapt_scan_apply(T *data, const T *tile, uint32_t n) {
+__global__ __launch_bounds__(SCAN_THREADS) void modeadapt_scan_apply(T *data, const T *tile, uint32_t n,
+                                                                     const uint32_t *n_dev) {
   __shared__ T lds[2 * SCAN_THREADS];
-  if (blockIdx.x * SCAN_TILE >= n) return;
-  const uint32_t i0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  T v[SCAN_ITEMS];
-  T s{};
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++) {
-    v[q] = i0 + q < n ? data[i0 + q] : T{};
-    s = s + v[q];
-  }
-  T total;
-  T run = tile[blockIdx.x] + block_exclusive(s, lds, total);
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++) {
-    if (i0 + q < n) data[i0 + q] = run;
-    run = run + v[q];
-  }
+  scan_apply_body(data, tile, n, n_dev, lds);
 }
-
-uint32_t scan_tiles_of(uint32_t n) { return std::max<uint32_t>(1, (n + SCAN_TILE - 1) / SCAN_TILE); }
-
 template <class T>
 hipError_t scan_exclusive(T *data, T *tile, uint32_t n, hipStream_t st) {
-  const uint32_t ntiles = scan_tiles_of(n);
-  hipLaunchKernelGGL(modeadapt_scan_reduce<T>, dim3(ntiles), dim3(SCAN_THREADS), 0, st, data, tile, n);
-  hipLaunchKernelGGL(modeadapt_scan_tiles<T>, dim3(1), dim3(SCAN_THREADS), 0, st, tile, ntiles);
-  hipLaunchKernelGGL(modeadapt_scan_apply<T>, dim3(ntiles), dim3(SCAN_THREADS), 0, st, data, tile, n);
-  return hipGetLastError();
+  return scan_exclusive(ScanKernels<T>{modeadapt_scan_reduce<T>, modeadapt_scan_tiles<T>, modeadapt_scan_apply<T>}, data,
+                        tile, n, nullptr, st);
 }
 
 // ------------------------------------------------------------------------------------------ per-packet passes
@@ -359,10 +296,6 @@ __global__ __launch_bounds__(256) void modeadapt_count(MaDev d, MaRun r, uint32_
   }
 }
 
-uint32_t blocks_for(uint32_t work, uint32_t per_block, uint32_t most) {
-  return std::min(most, std::max<uint32_t>(1, (work + per_block - 1) / per_block));
-}
-
 }  // namespace
 
 void modeadapt_host_table(uint32_t *tab) {
@@ -374,13 +307,7 @@ void modeadapt_host_table(uint32_t *tab) {
 }
 
 size_t modeadapt_layout(MaDev &d, void *base) {
-  size_t at = 0;
-  auto take = [&](auto *&ptr, size_t count) {
-    using E = std::remove_reference_t<decltype(*ptr)>;
-    at = (at + 255) & ~(size_t)255;
-    ptr = base ? (E *)((char *)base + at) : nullptr;
-    at += count * sizeof(E);
-  };
+  LayoutTaker take{base};
   const size_t n = d.max_ts, nt = scan_tiles_of(d.max_ts) + 1;
   take(d.res, MA_R_WORDS);
   take(d.flags, n);
@@ -392,7 +319,7 @@ size_t modeadapt_layout(MaDev &d, void *base) {
   take(d.unit, n);
   take(d.mask, 256);
   take(d.crc, 256);
-  return at;
+  return take.at;
 }
 
 hipError_t modeadapt_launch(const MaDev &d, const MaRun &r, hipStream_t st) {

@@ -1,10 +1,10 @@
 // MPE-FEC encapsulation (this project's reading of EN 301 192 clause 9) on gfx950: a device buffer of IP datagrams and
 // an offset table -> per closed frame its MPE sections, then Reed-Solomon columns in MPE-FEC sections, in 188-byte TS
 // packets.  Semantics: include/dvbt2ll_hip.h; tests/mpefec_ref.py is the sequential restatement every output is
-// compared with.  The scan, CRC and emit code is mpe_kernels.hip's, copied and made to run over a list of sections
-// (items) of two kinds instead of over the PDUs.  Passes of one run, all on the caller's stream:
+// compared with.  The units ts_section_packer.h packs are a list of sections (items) of two kinds, closed as the MPE
+// handle's (MINFREE 1).  Passes of one run, all on the caller's stream:
 //   measure    a lane per PDU: validity, the MAC's two header bytes, the length p; (p << 25 | 1) for the sum scan
-//   sum scan   64-bit, three launches: before each PDU the valid bytes and the valid PDUs of the call
+//   sum scan   64-bit (dev_scan.h): before each PDU the valid bytes and the valid PDUs of the call
 //   next       a lane per PDU: where a frame that begins here would end (two binary searches in the sums), and whether
 //              the call closes it
 //   chain      one lane follows the frames from the start, up to max_frames of them; it also settles the start's
@@ -14,17 +14,21 @@
 //   rs         a workgroup per 256 rows of a frame, a lane per row: the row's 64 parity bytes live in 16 VGPRs; per
 //              symbol the feedback byte picks a 64-byte row of a 16 KiB LDS table (128-bit reads) that is added to the
 //              parities shifted by one byte
-//   maps, compose, walk   the state scan over the items (packing 0 runs it with a step that starts every section in
-//              a packet of its own)
+//   maps, compose, walk   the packer's state scan over the items (packing 0 runs it with a step that starts every
+//              section in a packet of its own)
 //   crc        MPE sections of up to CRC_LANE_MAX bytes a lane each; longer ones and every MPE-FEC section a wavefront
-//   emit       as the MPE handle's
+//   emit       the packer's
 //   count      the resume position, and the counters of the frames wholly sent
 // A closed frame past max_frames is computed as well (the lookahead frame): its sections decide the packet in which
 // the frame before it ends, and no packet that begins behind that frame's last byte is emitted.
 #include "mpefec_kernels.h"
 
 #include <algorithm>
-#include <type_traits>
+
+#include "crc32_mpeg2.h"
+#include "dev_scan.h"
+#include "host_util.h"
+#include "ts_section_packer.h"
 
 namespace t2 {
 
@@ -32,8 +36,7 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr uint32_t MF_POLY = 0x04C11DB7u;
-enum : uint32_t { M_LEN = 0xFFFFu, M_MAPPED = 1u << 29, M_SKIP_TYPE = 1u << 30, M_SKIP_LEN = 1u << 31 };
+enum : uint32_t { M_LEN = PK_LEN, M_MAPPED = 1u << 29, M_SKIP_TYPE = 1u << 30, M_SKIP_LEN = 1u << 31 };
 enum : uint32_t { I_FEC = 1u << 31 };
 // d.ctl: packets completed, the end state, the start's section_byte as taken, long sections, frames computed (the
 // lookahead frame included), frames the call may send (0: no lookahead frame, all of them), the start's section as
@@ -41,89 +44,33 @@ enum : uint32_t { I_FEC = 1u << 31 };
 enum : int { C_T = 0, C_Q, C_S, C_NLONG, C_F, C_LOOK, C_IS, C_NI, C_REST };
 constexpr int KEY_SHIFT = 25;                     // the sums' low bits count the valid PDUs (up to 2^24)
 constexpr u64 KEY_COUNT = (1ull << KEY_SHIFT) - 1;
-constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 4, SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
-constexpr int ST_Q = MF_MAP_STATES, ST_TILE = MF_TILE, ST_ROUND = 32, ST_THREADS = 512;
-constexpr int ST_PER = (ST_ROUND * ST_Q + ST_THREADS - 1) / ST_THREADS;
+static_assert(MF_MAP_STATES == PK_STATES && MF_TILE == PK_TILE, "the layout is sized for the packer's maps");
+constexpr int MINFREE = 1;
 constexpr uint32_t CRC_LANE_MAX = 192;
 constexpr uint32_t HL = MF_HEADER;
-constexpr uint32_t EMIT_PKTS = 64;
 constexpr uint32_t COUNT_BLOCKS = 64;
 constexpr uint32_t RS_ROWS = 256;                 // rows (lanes) per workgroup of the RS pass
 
 __device__ inline uint32_t cnt_of(u64 k) { return (uint32_t)(k & KEY_COUNT); }
 __device__ inline u64 sum_of(u64 k) { return k >> KEY_SHIFT; }
 
-// ------------------------------------------------------------------------------------------ device-wide sum scan
-__device__ u64 block_exclusive(u64 v, u64 *lds, u64 &total) {
-  const int t = threadIdx.x;
-  u64 *a = lds, *b = lds + SCAN_THREADS;
-  a[t] = v;
-  __syncthreads();
-  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-    u64 x = a[t];
-    if (t >= d) x = a[t - d] + x;
-    b[t] = x;
-    __syncthreads();
-    u64 *s = a; a = b; b = s;
-  }
-  total = a[SCAN_THREADS - 1];
-  const u64 ex = t ? a[t - 1] : 0;
-  __syncthreads();
-  return ex;
-}
-
-__global__ __launch_bounds__(SCAN_THREADS) void mf_scan_reduce(const u64 *in, u64 *tile, uint32_t n) {
+__global__ __launch_bounds__(SCAN_THREADS) void mf_scan_reduce(const u64 *in, u64 *tile, uint32_t n, const uint32_t *n_dev) {
   __shared__ u64 lds[SCAN_THREADS];
-  const uint32_t i0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  u64 s = 0;
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++)
-    if (i0 + q < n) s += in[i0 + q];
-  lds[threadIdx.x] = s;
-  __syncthreads();
-  for (int dd = SCAN_THREADS / 2; dd > 0; dd >>= 1) {
-    if ((int)threadIdx.x < dd) lds[threadIdx.x] += lds[threadIdx.x + dd];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) tile[blockIdx.x] = lds[0];
+  scan_reduce_body(in, tile, n, n_dev, lds);
 }
-
-// one workgroup: tile sums -> exclusive tile offsets in place.  The second round (tiles 256 and up) begins at the
-// loop's second pass, with the tiles before it in carry.
 __global__ __launch_bounds__(SCAN_THREADS) void mf_scan_tiles(u64 *tile, uint32_t ntiles) {
   __shared__ u64 lds[2 * SCAN_THREADS];
-  u64 carry = 0;
-  for (uint32_t b = 0; b < ntiles; b += SCAN_THREADS) {
-    const uint32_t i = b + threadIdx.x;
-    const u64 v = i < ntiles ? tile[i] : 0;
-    u64 total;
-    const u64 ex = block_exclusive(v, lds, total);
-    if (i < ntiles) tile[i] = carry + ex;
-    carry += total;
-  }
+  scan_tiles_body(tile, ntiles, lds);
 }
-
-__global__ __launch_bounds__(SCAN_THREADS) void mf_scan_apply(u64 *data, const u64 *tile, uint32_t n) {
+__global__ __launch_bounds__(SCAN_THREADS) void mf_scan_apply(u64 *data, const u64 *tile, uint32_t n, const uint32_t *n_dev) {
   __shared__ u64 lds[2 * SCAN_THREADS];
-  const uint32_t i0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  u64 v[SCAN_ITEMS];
-  u64 s = 0;
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++) {
-    v[q] = i0 + q < n ? data[i0 + q] : 0;
-    s += v[q];
-  }
-  u64 total;
-  u64 run = tile[blockIdx.x] + block_exclusive(s, lds, total);
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++) {
-    if (i0 + q < n) data[i0 + q] = run;
-    run += v[q];
-  }
+  scan_apply_body(data, tile, n, n_dev, lds);
 }
+constexpr ScanKernels<u64> MF_SCAN{mf_scan_reduce, mf_scan_tiles, mf_scan_apply};
 
-uint32_t scan_tiles_of(uint32_t n) { return std::max<uint32_t>(1, (n + SCAN_TILE - 1) / SCAN_TILE); }
-uint32_t state_tiles_of(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + ST_TILE - 1) / ST_TILE); }
+uint32_t state_tiles_of(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + PK_TILE - 1) / PK_TILE); }
+// the items, as the control words count them
+__device__ inline PkUnits mf_units(const MfDev &d) { return PkUnits{d.ilen, d.pkt, d.at, d.ctl[C_NI]}; }
 
 // ------------------------------------------------------------------------------------------ measure
 // lanes 0 .. n: lane n writes the sums' last entry only
@@ -377,143 +324,20 @@ __global__ __launch_bounds__(RS_ROWS) void mf_rs(MfDev d) {
 }
 
 // ------------------------------------------------------------------------------------------ the state scan
-// one section of n bytes entered in state q with pk packets completed; cont: it continues an earlier call's section
-__device__ inline void mf_step(uint32_t n, bool cont, bool packing, uint32_t &q, uint32_t &pk) {
-  if (!n) return;
-  if (!packing) {   // every section starts a packet behind pointer_field 0
-    pk += cont ? (n + 183) / 184 : (n + 184) / 184;
-    q = 0;
-    return;
-  }
-  uint32_t rem = n;
-  if (!cont) {
-    const uint32_t a = q ? q : 1, space = 184 - a;
-    if (n <= space) {
-      const uint32_t e = a + n;
-      if (e == 184) { pk++; q = 0; }
-      else q = e;
-      return;
-    }
-    pk++;
-    rem = n - space;
-  }
-  pk += rem / 184;
-  rem %= 184;
-  if (rem == 0) q = 0;
-  else if (rem == 183) { pk++; q = 0; }
-  else q = 1 + rem;
+__global__ __launch_bounds__(PK_THREADS) void mf_maps(MfDev d) {
+  const uint32_t N = d.ctl[C_NI];
+  if (blockIdx.x * PK_TILE >= N) return;
+  pk_maps_body<MINFREE>(d.ilen, N, d.ctl[C_S], d.packing, d.maps);
 }
 
-__device__ inline void mf_tile_lens(const MfDev &d, uint32_t N, uint32_t base, uint32_t s, uint16_t *ln) {
-  for (uint32_t k = threadIdx.x; k < (uint32_t)ST_TILE; k += blockDim.x) {
-    const uint32_t i = base + k;
-    uint32_t v = i < N ? d.ilen[i] & M_LEN : 0;
-    if (i == 0 && v) v -= s;
-    ln[k] = (uint16_t)v;
-  }
-  __syncthreads();
+__global__ __launch_bounds__(PK_COMPOSE_THREADS) void mf_compose(MfDev d) {
+  pk_compose_body(d.maps, (d.ctl[C_NI] + PK_TILE - 1) / PK_TILE, d.ent_q, d.ent_pk, &d.ctl[C_T], &d.ctl[C_Q]);
 }
 
-__global__ __launch_bounds__(256) void mf_maps(MfDev d) {
-  __shared__ uint16_t ln[ST_TILE];
-  const uint32_t N = d.ctl[C_NI], s = d.ctl[C_S], base = blockIdx.x * ST_TILE;
-  if (base >= N) return;
-  mf_tile_lens(d, N, base, s, ln);
-  if (threadIdx.x >= (uint32_t)ST_Q) return;
-  uint32_t q = threadIdx.x, pk = 0;
-  mf_step(ln[0], s != 0 && base == 0, d.packing, q, pk);
-  for (int k = 1; k < ST_TILE; k++) mf_step(ln[k], false, d.packing, q, pk);
-  d.maps[(size_t)blockIdx.x * ST_Q + threadIdx.x] = (pk << 8) | q;
-}
-
-__global__ __launch_bounds__(ST_THREADS) void mf_compose(MfDev d) {
-  __shared__ uint32_t buf[2][ST_ROUND * ST_Q];
-  const uint32_t N = d.ctl[C_NI], ntiles = (N + ST_TILE - 1) / ST_TILE;
-  const uint32_t total = ntiles * ST_Q;
-  uint32_t cq = 0, cpk = 0;
-  uint32_t nxt[ST_PER];
-#pragma unroll
-  for (int k = 0; k < ST_PER; k++) {
-    const uint32_t e = threadIdx.x + k * ST_THREADS;
-    nxt[k] = e < total ? d.maps[e] : e % ST_Q;
-  }
-  // the second round (tiles ST_ROUND and up) begins at this loop's second pass
-  for (uint32_t b = 0; b < ntiles; b += ST_ROUND) {
-    uint32_t *A = buf[0], *B = buf[1];
-#pragma unroll
-    for (int k = 0; k < ST_PER; k++) {
-      const uint32_t e = threadIdx.x + k * ST_THREADS;
-      if (e < (uint32_t)(ST_ROUND * ST_Q)) A[e] = nxt[k];
-    }
-    if (b + ST_ROUND < ntiles) {
-#pragma unroll
-      for (int k = 0; k < ST_PER; k++) {
-        const uint32_t e = threadIdx.x + k * ST_THREADS, g = (b + ST_ROUND) * ST_Q + e;
-        nxt[k] = g < total ? d.maps[g] : e % ST_Q;
-      }
-    }
-    __syncthreads();
-    for (int dd = 1; dd < ST_ROUND; dd <<= 1) {
-#pragma unroll
-      for (int k = 0; k < ST_PER; k++) {
-        const uint32_t e = threadIdx.x + k * ST_THREADS;
-        if (e < (uint32_t)(ST_ROUND * ST_Q)) {
-          const uint32_t t = e / ST_Q;
-          uint32_t v = A[e];
-          if (t >= (uint32_t)dd) {
-            const uint32_t f = A[e - dd * ST_Q];
-            v = (f & ~255u) + A[t * ST_Q + (f & 255u)];
-          }
-          B[e] = v;
-        }
-      }
-      __syncthreads();
-      uint32_t *x = A; A = B; B = x;
-    }
-    const uint32_t t = threadIdx.x;
-    if (t < (uint32_t)ST_ROUND && b + t < ntiles) {
-      uint32_t eq = cq, epk = cpk;
-      if (t) {
-        const uint32_t f = A[(t - 1) * ST_Q + cq];
-        eq = f & 255u;
-        epk = cpk + (f >> 8);
-      }
-      d.ent_q[b + t] = eq;
-      d.ent_pk[b + t] = epk;
-    }
-    const uint32_t f = A[(ST_ROUND - 1) * ST_Q + cq];
-    cq = f & 255u;
-    cpk += f >> 8;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    d.ctl[C_T] = cpk;
-    d.ctl[C_Q] = cq;
-  }
-}
-
-__global__ __launch_bounds__(256) void mf_walk(MfDev d) {
-  __shared__ uint16_t ln[ST_TILE];
-  __shared__ uint32_t pk_s[ST_TILE];
-  __shared__ uint8_t at_s[ST_TILE];
-  const uint32_t N = d.ctl[C_NI], s = d.ctl[C_S], base = blockIdx.x * ST_TILE;
-  if (base >= N) return;
-  mf_tile_lens(d, N, base, s, ln);
-  if (threadIdx.x == 0) {
-    uint32_t q = d.ent_q[blockIdx.x], pk = d.ent_pk[blockIdx.x];
-    for (int k = 0; k < ST_TILE; k++) {
-      const bool cont = k == 0 && base == 0 && s != 0;
-      pk_s[k] = pk;
-      at_s[k] = (uint8_t)(cont ? 0 : q ? q : 1);
-      mf_step(ln[k], cont, d.packing, q, pk);
-    }
-  }
-  __syncthreads();
-  for (uint32_t k = threadIdx.x; k < (uint32_t)ST_TILE; k += 256)
-    if (base + k < N) {
-      d.pkt[base + k] = pk_s[k];
-      d.at[base + k] = at_s[k];
-    }
+__global__ __launch_bounds__(PK_THREADS) void mf_walk(MfDev d) {
+  const PkUnits u = mf_units(d);
+  if (blockIdx.x * PK_TILE >= u.N) return;
+  pk_walk_body<MINFREE>(u, d.ctl[C_S], d.packing, d.ent_q, d.ent_pk);
 }
 
 // ------------------------------------------------------------------------------------------ section bytes
@@ -524,70 +348,38 @@ __device__ inline const uint8_t *mf_payload(const MfDev &d, const MfRun &r, uint
   return (d.ilen[x] & I_FEC) ? d.par + (size_t)d.isrc[x] * d.rows : r.pdu + r.off[r.i0 + d.isrc[x]];
 }
 
-__device__ inline uint32_t mf_section_byte(const MfDev &d, const MfRun &r, uint32_t j, uint32_t k) {
-  const uint32_t n = d.ilen[j] & M_LEN;
-  if (k < HL) return mf_header_byte(d.ihdr + 3 * (size_t)j, k);
-  if (k + 4 < n) return mf_payload(d, r, j)[k - HL];
-  return (d.icrc[j] >> (8 * (n - 1 - k))) & 255;
-}
-
-// bytes k .. k + 3 of item j's section (all inside it): a header word; one aligned word of the payload, or two joined
-// by a shift, where all four are payload bytes and the words lie inside the payload's buffer; bytes otherwise
-__device__ inline uint32_t mf_section_word(const MfDev &d, const MfRun &r, uint32_t j, uint32_t k) {
-  const uint32_t w0 = d.ilen[j], n = w0 & M_LEN;
-  if (k < HL && (k & 3) == 0) return d.ihdr[3 * (size_t)j + (k >> 2)];
-  if (k >= HL && k + 8 <= n) {
-    const uint8_t *src = mf_payload(d, r, j) + (k - HL);
-    const uint32_t sh = (uint32_t)((uintptr_t)src & 3);
-    const uint8_t *a = src - sh;
-    if (sh == 0) return *(const uint32_t *)a;
-    const uint8_t *lo = (w0 & I_FEC) ? d.par : r.pdu;
-    const uint8_t *hi = (w0 & I_FEC) ? d.par + (size_t)d.ctl[C_F] * d.K * d.rows : r.pdu + r.pdu_len;
-    if (a >= lo && a + 8 <= hi) {
-      const uint32_t l = *(const uint32_t *)a, h = *(const uint32_t *)(a + 4);
-      return (l >> (8 * sh)) | (h << (32 - 8 * sh));
-    }
+// the packer's source of section bytes
+struct MfSrc {
+  const MfDev &d;
+  const MfRun &r;
+  __device__ uint32_t byte(uint32_t j, uint32_t k) const {
+    const uint32_t n = d.ilen[j] & M_LEN;
+    if (k < HL) return mf_header_byte(d.ihdr + 3 * (size_t)j, k);
+    if (k + 4 < n) return mf_payload(d, r, j)[k - HL];
+    return (d.icrc[j] >> (8 * (n - 1 - k))) & 255;
   }
-  uint32_t w = 0;
-  for (uint32_t q = 0; q < 4; q++) w |= mf_section_byte(d, r, j, k + q) << (8 * q);
-  return w;
-}
+  // bytes k .. k + 3 of item j's section (all inside it): a header word; a word of the payload's buffer where all four
+  // are payload bytes; bytes otherwise
+  __device__ uint32_t word(uint32_t j, uint32_t k) const {
+    const uint32_t w0 = d.ilen[j], n = w0 & M_LEN;
+    uint32_t w = 0;
+    if (k < HL && (k & 3) == 0) return d.ihdr[3 * (size_t)j + (k >> 2)];
+    if (k >= HL && k + 8 <= n) {
+      const uint8_t *lo = (w0 & I_FEC) ? d.par : r.pdu;
+      const uint8_t *hi = (w0 & I_FEC) ? d.par + (size_t)d.ctl[C_F] * d.K * d.rows : r.pdu + r.pdu_len;
+      if (pk_read4(mf_payload(d, r, j) + (k - HL), lo, hi, w)) return w;
+    }
+    for (uint32_t q = 0; q < 4; q++) w |= byte(j, k + q) << (8 * q);
+    return w;
+  }
+};
 
 // ------------------------------------------------------------------------------------------ CRC-32
-__device__ inline uint32_t gf_mul(uint32_t a, uint32_t b) {   // a(x) b(x) mod G, bit 31 = x^31
-  uint32_t r = 0;
-  for (int i = 31; i >= 0; i--) {
-    r = (r << 1) ^ ((r >> 31) ? MF_POLY : 0u);
-    if ((b >> i) & 1) r ^= a;
-  }
-  return r;
-}
-
-__device__ inline uint32_t crc_byte(uint32_t crc, uint32_t b, const uint32_t *tab) {
-  return (crc << 8) ^ tab[(crc >> 24) ^ b];
-}
-
-__device__ inline uint32_t crc_run(uint32_t crc, const uint8_t *p, uint32_t n, const uint32_t *tab) {
-  while (n && ((uintptr_t)p & 3)) {
-    crc = crc_byte(crc, *p++, tab);
-    n--;
-  }
-  for (; n >= 4; n -= 4, p += 4) {
-    const uint32_t w = *(const uint32_t *)p;
-    crc = crc_byte(crc, w & 255, tab);
-    crc = crc_byte(crc, (w >> 8) & 255, tab);
-    crc = crc_byte(crc, (w >> 16) & 255, tab);
-    crc = crc_byte(crc, w >> 24, tab);
-  }
-  for (; n; n--) crc = crc_byte(crc, *p++, tab);
-  return crc;
-}
-
 // section bytes [lo, hi) of a section (hi <= n - 4): the header's (words h), then the payload's
 __device__ inline uint32_t crc_span(uint32_t crc, const uint32_t *h, const uint8_t *pay, uint32_t lo, uint32_t hi,
                                     const uint32_t *tab) {
-  for (; lo < hi && lo < HL; lo++) crc = crc_byte(crc, mf_header_byte(h, lo), tab);
-  if (lo < hi) crc = crc_run(crc, pay + (lo - HL), hi - lo, tab);
+  for (; lo < hi && lo < HL; lo++) crc = crc32m_byte(crc, mf_header_byte(h, lo), tab);
+  if (lo < hi) crc = crc32m_run(crc, pay + (lo - HL), hi - lo, tab);
   return crc;
 }
 
@@ -616,208 +408,42 @@ __global__ __launch_bounds__(256) void mf_crc_long(MfDev d, MfRun r) {
     const uint32_t nj = d.ilen[j] & M_LEN;
     if (nj <= CRC_LANE_MAX) continue;
     const uint8_t *pay = mf_payload(d, r, j);
-    // the T bytes are padded in front to 64 chunks of c bytes; the tree multiplies by x^(8 c 2^m) at level m; the
-    // initial 0xFFFFFFFF is added as 0xFFFFFFFF x^(8 T)
-    const uint32_t T = nj - 4, c = (T + 63) >> 6, pad = 64 * c - T;
-    int lo = (int)(lane * c) - (int)pad, hi = lo + (int)c;
-    if (lo < 0) lo = 0;
+    const uint32_t T = nj - 4;
+    int lo, hi;
+    const uint32_t c = crc32m_wave_chunk(lane, T, lo, hi);
     uint32_t crc = 0;
     if (hi > lo) crc = crc_span(0, d.ihdr + 3 * (size_t)j, pay, (uint32_t)lo, (uint32_t)hi, tab);
-    for (int lv = 0; lv < 6; lv++) {
-      const uint32_t other = __shfl_xor(crc, 1 << lv);
-      const bool right = (lane >> lv) & 1;
-      crc = gf_mul(right ? other : crc, xp[c << lv]) ^ (right ? crc : other);
-    }
-    crc ^= gf_mul(0xFFFFFFFFu, xp[T]);
+    crc = crc32m_wave_join(crc, lane, c, T, xp);
     if (lane == 0) d.icrc[j] = crc;
   }
 }
 
-// ------------------------------------------------------------------------------------------ the cut, positions
-struct MfCut {
-  uint32_t N;          // items
-  uint32_t T, q, s;    // packets completed, the end state, the start's section_byte
-  uint32_t E;          // packets emitted
-  bool flush;          // the call's flush, unless a lookahead frame follows
-  bool all;            // nothing of the items is left
-};
-
-__device__ inline MfCut mf_cut(const MfDev &d, const MfRun &r) {
-  MfCut c;
-  c.N = d.ctl[C_NI];
-  c.T = d.ctl[C_T];
-  c.q = d.ctl[C_Q];
-  c.s = d.ctl[C_S];
+// ------------------------------------------------------------------------------------------ the cut, emit
+// the call's flush counts unless a lookahead frame follows; all: nothing of the items is left
+__device__ inline PkCut mf_cut(const MfDev &d, const MfRun &r) {
   const uint32_t look = d.ctl[C_LOOK];
-  c.flush = r.flush && !look;
-  uint32_t det = c.T + (c.q && c.flush ? 1 : 0);
+  uint32_t lim = ~0u;
   if (look) {   // up to the packet the last frame to send ends in: the one before the lookahead frame's first section
                 // where that begins a packet, else the one it starts in (full: the lookahead frame is longer than it)
     const uint32_t x = cnt_of(d.pre[d.fs[look]]) + look * d.K - d.ctl[C_IS];
-    const uint32_t lim = d.pkt[x] + (d.at[x] != 1 ? 1 : 0);
-    if (lim < det) det = lim;
+    lim = d.pkt[x] + (d.at[x] != 1 ? 1 : 0);
   }
-  c.E = det < r.cap ? det : r.cap;
-  c.all = !look && c.E == det && (c.q == 0 || c.flush);
+  PkCut c = pk_cut(d.ctl[C_T], d.ctl[C_Q], d.ctl[C_S], r.flush && !look, r.cap, lim);
+  c.all = c.all && !look;
   return c;
 }
 
-struct MfPos { uint32_t jc, R, coff, jn; };
-
-__device__ inline MfPos mf_locate(const MfDev &d, uint32_t N, uint32_t s, uint32_t p) {
-  uint32_t lo = 0, hi = N;   // the first item whose first packet is p or later
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (d.pkt[mid] < p) lo = mid + 1;
-    else hi = mid;
-  }
-  MfPos ps{0, 0, 0, lo};
-  if (p == 0 && s && N) {   // the section an earlier call began
-    ps.R = (d.ilen[0] & M_LEN) - s;
-    ps.coff = s;
-    ps.jn = 1;
-  } else if (lo > 0) {
-    const uint32_t j = lo - 1, n = d.ilen[j] & M_LEN, sk = j == 0 ? s : 0;
-    const uint32_t consumed = (184 - d.at[j]) + 184 * (p - d.pkt[j] - 1);
-    ps.jc = j;
-    ps.coff = sk + consumed;
-    ps.R = n > ps.coff ? n - ps.coff : 0;
-  }
-  return ps;
-}
-
-// ------------------------------------------------------------------------------------------ emit
-struct MfRec {
-  uint32_t jc, jn, jend;
-  uint16_t R, coff;
-  uint8_t pusi, nb;
-};
-
-__device__ inline MfRec mf_record(const MfDev &d, const MfCut &c, uint32_t p, uint32_t &pad) {
-  const MfPos ps = mf_locate(d, c.N, c.s, p);
-  MfRec q;
-  q.jc = ps.jc;
-  q.jn = q.jend = ps.jn;
-  q.R = (uint16_t)ps.R;
-  q.coff = (uint16_t)ps.coff;
-  bool pusi;
-  if (!d.packing) pusi = ps.R == 0;
-  else pusi = !(ps.R >= 183 || (p == c.T && ps.R && c.q == 1 + ps.R));
-  q.pusi = pusi;
-  q.nb = 0;
-  if (!pusi) {
-    q.nb = (uint8_t)(ps.R < 184 ? ps.R : 184);
-    pad = 184 - q.nb;
-  } else {
-    uint32_t used = 1 + ps.R, x = ps.jn;
-    for (; x < c.N && d.pkt[x] == p; x++) {
-      const uint32_t n = d.ilen[x] & M_LEN;
-      if (n) used = d.at[x] + n < 184 ? d.at[x] + n : 184;
-    }
-    q.jend = x;
-    pad = 184 - used;
-  }
-  return q;
-}
-
-__device__ inline bool mf_resolve(const MfDev &d, const MfRec &q, uint32_t b, uint32_t &j, uint32_t &k, uint32_t &lit) {
-  lit = 0xFF;
-  if (!q.pusi) {
-    if (b >= q.nb) return false;
-    j = q.jc;
-    k = q.coff + b;
-    return true;
-  }
-  if (b == 0) { lit = q.R; return false; }
-  if (b < 1u + q.R) {
-    j = q.jc;
-    k = q.coff + b - 1;
-    return true;
-  }
-  for (uint32_t x = q.jn; x < q.jend; x++) {
-    const uint32_t n = d.ilen[x] & M_LEN, a = d.at[x];
-    if (!n) continue;
-    if (a > b) break;
-    if (b < a + n) {
-      j = x;
-      k = b - a;
-      return true;
-    }
-  }
-  return false;
-}
-
-__device__ inline uint32_t mf_out_byte(const MfDev &d, const MfRun &r, const MfRec &q, uint32_t p, uint32_t o) {
-  if (o == 0) return 0x47;
-  if (o == 1) return ((uint32_t)q.pusi << 6) | ((uint32_t)d.pid >> 8);
-  if (o == 2) return (uint32_t)d.pid & 255;
-  if (o == 3) return 0x10 | ((r.cc + p) & 15);
-  uint32_t j, k, lit;
-  if (mf_resolve(d, q, o - 4, j, k, lit)) return mf_section_byte(d, r, j, k);
-  return lit;
-}
-
-__device__ inline uint32_t mf_out_word(const MfDev &d, const MfRun &r, const MfRec *rec, uint32_t p0, size_t g) {
-  const uint32_t p = (uint32_t)(g / 188), o = (uint32_t)(g - (size_t)p * 188);
-  if (o >= 4 && o + 4 <= 188) {
-    uint32_t j, k, lit;
-    if (mf_resolve(d, rec[p - p0], o - 4, j, k, lit) && k + 4 <= (d.ilen[j] & M_LEN)) return mf_section_word(d, r, j, k);
-  }
-  uint32_t w = 0;
-  for (uint32_t q = 0; q < 4; q++) {
-    const uint32_t pp = (uint32_t)((g + q) / 188), oo = (uint32_t)(g + q - (size_t)pp * 188);
-    w |= mf_out_byte(d, r, rec[pp - p0], pp, oo) << (8 * q);
-  }
-  return w;
-}
-
-// The grid covers the packets that PDUs lying side by side can become (mf_packet_estimate); where overlapping PDUs
-// make more, a workgroup takes more than one group of EMIT_PKTS: its second trip begins at the loop's second pass
-__global__ __launch_bounds__(256) void mf_emit(MfDev d, MfRun r) {
-  __shared__ MfRec rec[EMIT_PKTS];
-  __shared__ uint32_t cnt[2];
-  const MfCut c = mf_cut(d, r);
-  for (uint32_t p0 = blockIdx.x * EMIT_PKTS; p0 < c.E; p0 += gridDim.x * EMIT_PKTS) {
-    const uint32_t np = c.E - p0 < EMIT_PKTS ? c.E - p0 : EMIT_PKTS;
-    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    if (threadIdx.x < np) {
-      uint32_t pad = 0;
-      rec[threadIdx.x] = mf_record(d, c, p0 + threadIdx.x, pad);
-      if (rec[threadIdx.x].pusi) atomicAdd(&cnt[0], 1u);
-      if (pad) atomicAdd(&cnt[1], pad);
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && cnt[threadIdx.x])
-      atomicAdd(&d.res[threadIdx.x ? MF_R_PAD : MF_R_PUSI], (unsigned long long)cnt[threadIdx.x]);
-    const size_t g0 = (size_t)p0 * 188, g1 = g0 + (size_t)np * 188;
-    uint32_t head = (uint32_t)((16 - ((uintptr_t)(r.out + g0) & 15)) & 15);
-    if (head > g1 - g0) head = (uint32_t)(g1 - g0);
-    const uint32_t nchunks = 1 + (uint32_t)((g1 - g0 - head + 15) / 16);
-    for (uint32_t cidx = threadIdx.x; cidx < nchunks; cidx += 256) {
-      const size_t lo = cidx ? g0 + head + (size_t)(cidx - 1) * 16 : g0;
-      const size_t hi = cidx ? (g1 < lo + 16 ? g1 : lo + 16) : g0 + head;
-      if (hi <= lo) continue;
-      if (cidx && hi - lo == 16) {
-        uint32_t w[4];
-        for (uint32_t q = 0; q < 4; q++) w[q] = mf_out_word(d, r, rec, p0, lo + 4 * q);
-        *(uint4 *)(r.out + lo) = make_uint4(w[0], w[1], w[2], w[3]);
-      } else {
-        for (size_t g = lo; g < hi; g++) {
-          const uint32_t p = (uint32_t)(g / 188), o = (uint32_t)(g - (size_t)p * 188);
-          r.out[g] = (uint8_t)mf_out_byte(d, r, rec[p - p0], p, o);
-        }
-      }
-    }
-  }
+__global__ __launch_bounds__(PK_THREADS) void mf_emit(MfDev d, MfRun r) {
+  pk_emit_body<MINFREE>(MfSrc{d, r}, mf_units(d), mf_cut(d, r), d.packing, (uint32_t)d.pid, r.cc, r.out, &d.res[MF_R_PUSI],
+                        &d.res[MF_R_PAD]);
 }
 
 // ------------------------------------------------------------------------------------------ resume, counters
-__global__ __launch_bounds__(256) void mf_count(MfDev d, MfRun r) {
+__global__ __launch_bounds__(PK_THREADS) void mf_count(MfDev d, MfRun r) {
   __shared__ uint32_t hist[4];
   if (threadIdx.x < 4) hist[threadIdx.x] = 0;
   __syncthreads();
-  const MfCut c = mf_cut(d, r);
+  const PkCut c = mf_cut(d, r);
   const uint32_t F = d.ctl[C_F], rest = d.ctl[C_REST];
   // the resume position: the PDU (in this run's indices), the section of its frame, that section's bytes emitted, the
   // frames wholly sent
@@ -831,7 +457,7 @@ __global__ __launch_bounds__(256) void mf_count(MfDev d, MfRun r) {
       sb = r.section_byte;
     }
   } else if (!c.all) {
-    const MfPos ps = mf_locate(d, c.N, c.s, c.E);
+    const PkPos ps = pk_locate(mf_units(d), c.s, c.E);
     uint32_t x = ps.jn;   // every item is a section: the next one begins the packet when none runs on into it
     if (ps.R) {
       x = ps.jc;
@@ -890,16 +516,7 @@ uint64_t frames_estimate(const MfDev &d, uint64_t pdu_len, uint64_t n, uint64_t 
 }  // namespace
 
 void mf_host_tables(uint32_t *tab, uint32_t *rstab) {
-  for (uint32_t v = 0; v < 256; v++) {
-    uint32_t c = v << 24;
-    for (int i = 0; i < 8; i++) c = (c << 1) ^ ((c >> 31) ? MF_POLY : 0u);
-    tab[v] = c;
-  }
-  uint32_t p = 1;   // x^(8 n) mod G
-  for (int n = 0; n <= MF_MAX_SECTION; n++) {
-    tab[256 + n] = p;
-    p = (p << 8) ^ tab[p >> 24];
-  }
+  crc32m_host_tables(tab, MF_MAX_SECTION + 1);
   // g(x) = prod (x + 2^i), i = 0 .. 63, over GF(2^8) with 0x11D: g[0] .. g[64]
   uint32_t g[MF_RS_COLS + 1] = {1};
   uint32_t root = 1;
@@ -917,13 +534,7 @@ void mf_host_tables(uint32_t *tab, uint32_t *rstab) {
 }
 
 size_t mf_layout(MfDev &d, void *base) {
-  size_t at = 0;
-  auto take = [&](auto *&ptr, size_t count) {
-    using E = std::remove_reference_t<decltype(*ptr)>;
-    at = (at + 255) & ~(size_t)255;
-    ptr = base ? (E *)((char *)base + at) : nullptr;
-    at += count * sizeof(E);
-  };
+  LayoutTaker take{base};
   const size_t n = std::max<uint32_t>(d.max_pdus, 1), ni = std::max<uint32_t>(d.max_items, 1), nt = state_tiles_of(ni);
   take(d.res, MF_R_WORDS + MF_CTL_WORDS / 2);
   d.ctl = base ? (uint32_t *)(d.res + MF_R_WORDS) : nullptr;
@@ -940,14 +551,14 @@ size_t mf_layout(MfDev &d, void *base) {
   take(d.lng, ni);
   take(d.pkt, ni);
   take(d.at, ni);
-  take(d.maps, (size_t)nt * ST_Q);
+  take(d.maps, (size_t)nt * PK_STATES);
   take(d.ent_q, nt);
   take(d.ent_pk, nt);
   take(d.tab, MF_TAB_WORDS);
   take(d.rstab, MF_RS_WORDS);
   take(d.tbl, ((size_t)d.max_frames + 1) * d.D * d.rows);   // the lookahead frame's as well
   take(d.par, ((size_t)d.max_frames + 1) * d.K * d.rows + 8);
-  return at;
+  return take.at;
 }
 
 uint64_t mf_packet_estimate(const MfDev &d, uint64_t pdu_len, uint64_t n) {
@@ -969,11 +580,9 @@ hipError_t mf_launch(const MfDev &d, const MfRun &r, hipStream_t st) {
   const uint32_t fb = std::min<uint32_t>(d.max_frames + 1, r.n);                  // frames: whatever the offsets say
   const uint32_t fe = (uint32_t)frames_estimate(d, r.pdu_len, r.n, d.max_frames + 1);   // frames: PDUs side by side
   const uint64_t items = (uint64_t)r.n + (uint64_t)fb * d.K;                      // never more sections than this
-  const uint32_t nt = state_tiles_of(items), ntl = scan_tiles_of(r.n + 1);
+  const uint32_t nt = state_tiles_of(items);
   hipLaunchKernelGGL(mf_measure, dim3(nb1), dim3(256), 0, st, d, r);
-  hipLaunchKernelGGL(mf_scan_reduce, dim3(ntl), dim3(SCAN_THREADS), 0, st, d.pre, d.tile, r.n + 1);
-  hipLaunchKernelGGL(mf_scan_tiles, dim3(1), dim3(SCAN_THREADS), 0, st, d.tile, ntl);
-  hipLaunchKernelGGL(mf_scan_apply, dim3(ntl), dim3(SCAN_THREADS), 0, st, d.pre, d.tile, r.n + 1);
+  if ((e = scan_exclusive(MF_SCAN, d.pre, d.tile, r.n + 1, nullptr, st)) != hipSuccess) return e;
   hipLaunchKernelGGL(mf_next, dim3(nb), dim3(256), 0, st, d, r);
   hipLaunchKernelGGL(mf_chain, dim3(1), dim3(64), 0, st, d, r);
   if (fe) {
@@ -982,18 +591,18 @@ hipError_t mf_launch(const MfDev &d, const MfRun &r, hipStream_t st) {
     const uint64_t gw = (uint64_t)fe * (d.D * d.rows / 4);
     hipLaunchKernelGGL(mf_gather, dim3((uint32_t)std::min<uint64_t>((gw + 255) / 256, 1u << 20)), dim3(256), 0, st, d, r);
     hipLaunchKernelGGL(mf_rs, dim3(fe * (d.rows / RS_ROWS)), dim3(RS_ROWS), 0, st, d);
-    hipLaunchKernelGGL(mf_maps, dim3(nt), dim3(256), 0, st, d);
+    hipLaunchKernelGGL(mf_maps, dim3(nt), dim3(PK_THREADS), 0, st, d);
   }
-  hipLaunchKernelGGL(mf_compose, dim3(1), dim3(ST_THREADS), 0, st, d);
+  hipLaunchKernelGGL(mf_compose, dim3(1), dim3(PK_COMPOSE_THREADS), 0, st, d);
   if (fe) {
-    hipLaunchKernelGGL(mf_walk, dim3(nt), dim3(256), 0, st, d);
+    hipLaunchKernelGGL(mf_walk, dim3(nt), dim3(PK_THREADS), 0, st, d);
     hipLaunchKernelGGL(mf_crc_short, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, st, d, r);
     const uint64_t nlong = std::min<uint64_t>(r.n, r.pdu_len / (CRC_LANE_MAX - 15)) + (uint64_t)fe * d.K;
     hipLaunchKernelGGL(mf_crc_long, dim3((uint32_t)((nlong + 3) / 4)), dim3(256), 0, st, d, r);
     const uint64_t est = std::min<uint64_t>(r.cap, mf_packet_estimate(d, r.pdu_len, r.n));
-    if (est) hipLaunchKernelGGL(mf_emit, dim3((uint32_t)((est + EMIT_PKTS - 1) / EMIT_PKTS)), dim3(256), 0, st, d, r);
+    if (est) hipLaunchKernelGGL(mf_emit, dim3((uint32_t)((est + PK_EMIT_PKTS - 1) / PK_EMIT_PKTS)), dim3(PK_THREADS), 0, st, d, r);
   }
-  hipLaunchKernelGGL(mf_count, dim3(std::min(COUNT_BLOCKS, nb)), dim3(256), 0, st, d, r);
+  hipLaunchKernelGGL(mf_count, dim3(std::min(COUNT_BLOCKS, nb)), dim3(PK_THREADS), 0, st, d, r);
   return hipGetLastError();
 }
 

@@ -20,16 +20,13 @@
 
 #include <algorithm>
 
+#include "crc32_mpeg2.h"
+#include "dev_scan.h"
+#include "host_util.h"
+
 namespace t2 {
 
-namespace {
-
-enum : int { CTL_NC = 0, CTL_S, CTL_NS, CTL_NPTOT, CTL_NP, CTL_CUT, CTL_IEND, CTL_WORDS = 8 };
-enum : uint32_t { CLS_MASK = 7, CLS_PUSI = 8, CLS_BADPTR = 1u << 24 };
-enum : int { WHY_NONE = 0, WHY_OTHER_PLP = 1, WHY_LEN = 2 };
-constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 4, SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
-constexpr uint32_t POLY = 0x04C11DB7u;
-
+// found by the scan templates through argument-dependent lookup
 __host__ __device__ inline T2miV8 operator+(const T2miV8 &a, const T2miV8 &b) {
   T2miV8 r;
 #pragma unroll
@@ -37,99 +34,34 @@ __host__ __device__ inline T2miV8 operator+(const T2miV8 &a, const T2miV8 &b) {
   return r;
 }
 
-// ------------------------------------------------------------------------------------------ device-wide scan
-// exclusive scan of 256 per-thread values through LDS (2 x 256 entries); total = their sum
-template <class T>
-__device__ T block_exclusive(T v, T *lds, T &total) {
-  const int t = threadIdx.x;
-  T *a = lds, *b = lds + SCAN_THREADS;
-  a[t] = v;
-  __syncthreads();
-  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-    T x = a[t];
-    if (t >= d) x = a[t - d] + x;
-    b[t] = x;
-    __syncthreads();
-    T *s = a; a = b; b = s;
-  }
-  total = a[SCAN_THREADS - 1];
-  T ex = t ? a[t - 1] : T{};
-  __syncthreads();
-  return ex;
-}
+namespace {
 
-// n: host-known bound; n_dev (may be null): the live count on the device, entries at or past it read as zero
+enum : int { CTL_NC = 0, CTL_S, CTL_NS, CTL_NPTOT, CTL_NP, CTL_CUT, CTL_IEND, CTL_WORDS = 8 };
+enum : uint32_t { CLS_MASK = 7, CLS_PUSI = 8, CLS_BADPTR = 1u << 24 };
+enum : int { WHY_NONE = 0, WHY_OTHER_PLP = 1, WHY_LEN = 2 };
+
+// ------------------------------------------------------------------------------------------ device-wide scan
 template <class T>
 __global__ __launch_bounds__(SCAN_THREADS) void t2mi_scan_reduce(const T *in, T *tile, uint32_t n,
                                                                  const uint32_t *n_dev) {
   __shared__ T lds[2 * SCAN_THREADS];
-  const uint32_t lim = n_dev ? min(n, *n_dev) : n;
-  const uint32_t i0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  T s{};
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++) {
-    T x{};
-    if (i0 + q < lim) x = in[i0 + q];
-    s = s + x;
-  }
-  lds[threadIdx.x] = s;
-  __syncthreads();
-  for (int dd = SCAN_THREADS / 2; dd > 0; dd >>= 1) {
-    if ((int)threadIdx.x < dd) lds[threadIdx.x] = lds[threadIdx.x] + lds[threadIdx.x + dd];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) tile[blockIdx.x] = lds[0];
+  scan_reduce_body(in, tile, n, n_dev, lds);
 }
-
-// one workgroup: tile sums -> exclusive tile offsets in place, the grand total to tile[ntiles]
 template <class T>
 __global__ __launch_bounds__(SCAN_THREADS) void t2mi_scan_tiles(T *tile, uint32_t ntiles) {
   __shared__ T lds[2 * SCAN_THREADS];
-  T carry{};
-  for (uint32_t b = 0; b < ntiles; b += SCAN_THREADS) {
-    const uint32_t i = b + threadIdx.x;
-    T v = i < ntiles ? tile[i] : T{};
-    T total;
-    T ex = block_exclusive(v, lds, total);
-    if (i < ntiles) tile[i] = carry + ex;
-    carry = carry + total;
-  }
-  if (threadIdx.x == 0) tile[ntiles] = carry;
+  scan_tiles_body(tile, ntiles, lds);
 }
-
 template <class T>
 __global__ __launch_bounds__(SCAN_THREADS) void t2mi_scan_apply(T *data, const T *tile, uint32_t n,
                                                                 const uint32_t *n_dev) {
   __shared__ T lds[2 * SCAN_THREADS];
-  const uint32_t lim = n_dev ? min(n, *n_dev) : n;
-  if (blockIdx.x * SCAN_TILE >= lim) return;
-  const uint32_t i0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  T v[SCAN_ITEMS];
-  T s{};
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++) {
-    v[q] = i0 + q < lim ? data[i0 + q] : T{};
-    s = s + v[q];
-  }
-  T total;
-  T run = tile[blockIdx.x] + block_exclusive(s, lds, total);
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++) {
-    if (i0 + q < lim) data[i0 + q] = run;
-    run = run + v[q];
-  }
+  scan_apply_body(data, tile, n, n_dev, lds);
 }
-
 template <class T>
 hipError_t scan_exclusive(T *data, T *tile, uint32_t n, const uint32_t *n_dev, hipStream_t st) {
-  const uint32_t ntiles = std::max<uint32_t>(1, (n + SCAN_TILE - 1) / SCAN_TILE);
-  hipLaunchKernelGGL(t2mi_scan_reduce<T>, dim3(ntiles), dim3(SCAN_THREADS), 0, st, data, tile, n, n_dev);
-  hipLaunchKernelGGL(t2mi_scan_tiles<T>, dim3(1), dim3(SCAN_THREADS), 0, st, tile, ntiles);
-  hipLaunchKernelGGL(t2mi_scan_apply<T>, dim3(ntiles), dim3(SCAN_THREADS), 0, st, data, tile, n, n_dev);
-  return hipGetLastError();
+  return scan_exclusive(ScanKernels<T>{t2mi_scan_reduce<T>, t2mi_scan_tiles<T>, t2mi_scan_apply<T>}, data, tile, n, n_dev, st);
 }
-
-uint32_t scan_tiles_of(uint32_t n) { return std::max<uint32_t>(1, (n + SCAN_TILE - 1) / SCAN_TILE); }
 
 // ------------------------------------------------------------------------------------------ the TS layer
 __global__ __launch_bounds__(256) void t2mi_classify(T2miDev d, T2miRun r) {
@@ -255,36 +187,6 @@ __global__ __launch_bounds__(256) void t2mi_starts(T2miDev d, T2miRun r, uint32_
 }
 
 // ------------------------------------------------------------------------------------------ the T2-MI layer
-__device__ inline uint32_t gf_mul(uint32_t a, uint32_t b) {   // a(x) b(x) mod G, bit 31 = x^31
-  uint32_t r = 0;
-  for (int i = 31; i >= 0; i--) {
-    r = (r << 1) ^ ((r >> 31) ? POLY : 0u);
-    if ((b >> i) & 1) r ^= a;
-  }
-  return r;
-}
-
-__device__ inline uint32_t crc_byte(uint32_t crc, uint32_t b, const uint32_t *tab) {
-  return (crc << 8) ^ tab[(crc >> 24) ^ b];
-}
-
-// n bytes at p, all inside one TS payload: bytes up to a 4-byte boundary, aligned words, the rest
-__device__ inline uint32_t crc_run(uint32_t crc, const uint8_t *p, uint32_t n, const uint32_t *tab) {
-  while (n && ((uintptr_t)p & 3)) {
-    crc = crc_byte(crc, *p++, tab);
-    n--;
-  }
-  for (; n >= 4; n -= 4, p += 4) {
-    const uint32_t w = *(const uint32_t *)p;
-    crc = crc_byte(crc, w & 255, tab);
-    crc = crc_byte(crc, (w >> 8) & 255, tab);
-    crc = crc_byte(crc, (w >> 16) & 255, tab);
-    crc = crc_byte(crc, w >> 24, tab);
-  }
-  for (; n; n--) crc = crc_byte(crc, *p++, tab);
-  return crc;
-}
-
 __global__ __launch_bounds__(256) void t2mi_check(T2miDev d, T2miRun r) {
   __shared__ uint32_t tab[256];
   tab[threadIdx.x] = d.tab[threadIdx.x];
@@ -302,12 +204,9 @@ __global__ __launch_bounds__(256) void t2mi_check(T2miDev d, T2miRun r) {
       }
       continue;
     }
-    // CRC over all T bytes (0 when the trailing CRC matches).  The packet is padded in front to 64 chunks of c
-    // bytes: leading zeros leave a zero register unchanged, so every lane's chunk has the same length and the tree
-    // below multiplies by x^(8 c 2^m) at level m; the initial 0xFFFFFFFF is added as 0xFFFFFFFF x^(8 T).
-    const uint32_t c = (T + 63) >> 6, pad = 64 * c - T;
-    int lo = (int)(lane * c) - (int)pad, hi = lo + (int)c;
-    if (lo < 0) lo = 0;
+    // CRC over all T bytes (0 when the trailing CRC matches): a chunk per lane, joined
+    int lo, hi;
+    const uint32_t c = crc32m_wave_chunk(lane, T, lo, hi);
     uint32_t crc = 0;
     if (hi > lo) {
       uint32_t x = s + lo;
@@ -315,17 +214,12 @@ __global__ __launch_bounds__(256) void t2mi_check(T2miDev d, T2miRun r) {
       uint32_t kk = locate(d.c_base, k, x);
       while (x < xe) {
         const uint32_t seg_end = min(xe, d.c_base[kk + 1]);
-        crc = crc_run(crc, r.ts + d.c_off[kk] + (x - d.c_base[kk]), seg_end - x, tab);
+        crc = crc32m_run(crc, r.ts + d.c_off[kk] + (x - d.c_base[kk]), seg_end - x, tab);
         x = seg_end;
         kk++;
       }
     }
-    for (int m = 0; m < 6; m++) {
-      const uint32_t other = __shfl_xor(crc, 1 << m);
-      const bool right = (lane >> m) & 1;
-      crc = gf_mul(right ? other : crc, xp[c << m]) ^ (right ? crc : other);
-    }
-    crc ^= gf_mul(0xFFFFFFFFu, xp[T]);
+    crc = crc32m_wave_join(crc, lane, c, T, xp);
     // a discontinuity inside the packet: at a contributing TS packet after k that begins before s + T
     int bad = 0;
     for (uint32_t kk = k + 1 + lane; kk < nc && d.c_base[kk] < s + T; kk += 64) bad |= d.c_disc[kk];
@@ -465,33 +359,14 @@ __global__ __launch_bounds__(256) void t2mi_count_ts(T2miDev d, T2miRun r) {
     atomicAdd(&d.res[T2MI_R_TS + threadIdx.x], (unsigned long long)hist[threadIdx.x]);
 }
 
-uint32_t blocks_for(uint32_t work, uint32_t per_block, uint32_t most) {
-  return std::min(most, std::max<uint32_t>(1, (work + per_block - 1) / per_block));
-}
-
 }  // namespace
 
 void t2mi_host_tables(uint32_t *tab) {
-  for (uint32_t v = 0; v < 256; v++) {
-    uint32_t c = v << 24;
-    for (int i = 0; i < 8; i++) c = (c << 1) ^ ((c >> 31) ? POLY : 0u);
-    tab[v] = c;
-  }
-  uint32_t p = 1;   // x^(8 n) mod G
-  for (int n = 0; n <= T2MI_MAX_T; n++) {
-    tab[256 + n] = p;
-    p = (p << 8) ^ tab[p >> 24];
-  }
+  crc32m_host_tables(tab, T2MI_MAX_T + 1);
 }
 
 size_t t2mi_layout(T2miDev &d, void *base) {
-  size_t at = 0;
-  auto take = [&](auto *&ptr, size_t count) {
-    using E = std::remove_reference_t<decltype(*ptr)>;
-    at = (at + 255) & ~(size_t)255;
-    ptr = base ? (E *)((char *)base + at) : nullptr;
-    at += count * sizeof(E);
-  };
+  LayoutTaker take{base};
   const size_t n = d.max_ts, mp = d.max_packets;
   take(d.res, T2MI_R_WORDS + CTL_WORDS);   // ctl follows res: one memset clears both
   d.ctl = base ? (uint32_t *)(d.res + T2MI_R_WORDS) : nullptr;
@@ -511,7 +386,7 @@ size_t t2mi_layout(T2miDev &d, void *base) {
   take(d.tile_c, scan_tiles_of((uint32_t)mp) + 1);
   take(d.table, mp);
   take(d.tab, T2MI_TAB_WORDS);
-  return at;
+  return take.at;
 }
 
 hipError_t t2mi_launch(const T2miDev &d, const T2miRun &r, hipStream_t st) {

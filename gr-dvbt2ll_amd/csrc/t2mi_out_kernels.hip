@@ -17,42 +17,14 @@
 
 #include <algorithm>
 
+#include "crc32_mpeg2.h"
+#include "host_util.h"
+
 namespace t2 {
 
 namespace {
 
-constexpr uint32_t POLY = 0x04C11DB7u;
 constexpr uint32_t CRC_MAX_BLOCKS = 4096, EMIT_MAX_BLOCKS = 2048, EMIT_RUN = 8;
-
-__device__ inline uint32_t gf_mul(uint32_t a, uint32_t b) {   // a(x) b(x) mod G, bit 31 = x^31
-  uint32_t r = 0;
-  for (int i = 31; i >= 0; i--) {
-    r = (r << 1) ^ ((r >> 31) ? POLY : 0u);
-    if ((b >> i) & 1) r ^= a;
-  }
-  return r;
-}
-
-__device__ inline uint32_t crc_byte(uint32_t crc, uint32_t b, const uint32_t *tab) {
-  return (crc << 8) ^ tab[(crc >> 24) ^ b];
-}
-
-// n bytes at p: bytes up to a 4-byte boundary, aligned words, the rest
-__device__ inline uint32_t crc_run(uint32_t crc, const uint8_t *p, uint32_t n, const uint32_t *tab) {
-  while (n && ((uintptr_t)p & 3)) {
-    crc = crc_byte(crc, *p++, tab);
-    n--;
-  }
-  for (; n >= 4; n -= 4, p += 4) {
-    const uint32_t w = *(const uint32_t *)p;
-    crc = crc_byte(crc, w & 255, tab);
-    crc = crc_byte(crc, (w >> 8) & 255, tab);
-    crc = crc_byte(crc, (w >> 16) & 255, tab);
-    crc = crc_byte(crc, w >> 24, tab);
-  }
-  for (; n; n--) crc = crc_byte(crc, *p++, tab);
-  return crc;
-}
 
 // ------------------------------------------------------------------------------------------ one T2-MI packet
 // the source bytes of packet pk in frame fc of the call: a BBFRAME, or an auxiliary payload
@@ -103,13 +75,9 @@ __global__ __launch_bounds__(256) void t2mi_out_crc(T2moDev d, T2moRun r) {
   for (uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6); g < r.G; g += nw) {
     const uint32_t fc = g / d.P;
     const T2moPkt pk = d.pkt[g - fc * d.P];
-    // the body is padded in front to 64 chunks of c bytes: leading zeros leave a zero register unchanged, so every
-    // lane's chunk has the same length and the tree below multiplies by x^(8 c 2^m) at level m; the initial
-    // 0xFFFFFFFF is added as 0xFFFFFFFF x^(8 Tb)
-    const uint32_t Tb = pk.T - 4, c = (Tb + 63) >> 6, pad = 64 * c - Tb;
-    int lo = (int)(lane * c) - (int)pad;
-    const int hi = lo + (int)c;
-    if (lo < 0) lo = 0;
+    const uint32_t Tb = pk.T - 4;
+    int lo, hi;
+    const uint32_t c = crc32m_wave_chunk(lane, Tb, lo, hi);   // the body: a chunk per lane, joined below
     uint32_t slo, shi;
     pkt_source_span(pk, slo, shi);
     const uint8_t *src = pkt_source(d, r, pk, fc);
@@ -117,19 +85,14 @@ __global__ __launch_bounds__(256) void t2mi_out_crc(T2moDev d, T2moRun r) {
     for (uint32_t i = (uint32_t)lo; (int)i < hi;) {
       if (i >= slo && i < shi) {
         const uint32_t n = min((uint32_t)hi, shi) - i;
-        crc = crc_run(crc, src + (i - slo), n, tab);
+        crc = crc32m_run(crc, src + (i - slo), n, tab);
         i += n;
       } else {
-        crc = crc_byte(crc, body_byte(d, r, pk, fc, g, i), tab);
+        crc = crc32m_byte(crc, body_byte(d, r, pk, fc, g, i), tab);
         i++;
       }
     }
-    for (int m = 0; m < 6; m++) {
-      const uint32_t other = __shfl_xor(crc, 1 << m);
-      const bool right = (lane >> m) & 1;
-      crc = gf_mul(right ? other : crc, xp[c << m]) ^ (right ? crc : other);
-    }
-    crc ^= gf_mul(0xFFFFFFFFu, xp[Tb]);
+    crc = crc32m_wave_join(crc, lane, c, Tb, xp);
     if (lane == 0) d.crc[g] = crc;
   }
 }
@@ -267,23 +230,10 @@ __global__ __launch_bounds__(256) void t2mi_out_emit(T2moDev d, T2moRun r) {
   }
 }
 
-uint32_t blocks_for(uint32_t work, uint32_t per_block, uint32_t most) {
-  return std::min(most, std::max<uint32_t>(1, (work + per_block - 1) / per_block));
-}
-
 }  // namespace
 
 void t2mo_host_tables(uint32_t *tab) {
-  for (uint32_t v = 0; v < 256; v++) {
-    uint32_t c = v << 24;
-    for (int i = 0; i < 8; i++) c = (c << 1) ^ ((c >> 31) ? POLY : 0u);
-    tab[v] = c;
-  }
-  uint32_t p = 1;   // x^(8 n) mod G
-  for (int n = 0; n <= T2MO_MAX_T; n++) {
-    tab[256 + n] = p;
-    p = (p << 8) ^ tab[p >> 24];
-  }
+  crc32m_host_tables(tab, T2MO_MAX_T + 1);
 }
 
 void t2mo_host_walk(const T2moDev &d, const T2moPkt *pkt, std::vector<uint32_t> &tq, std::vector<uint8_t> &td,
@@ -326,20 +276,14 @@ void t2mo_host_walk(const T2moDev &d, const T2moPkt *pkt, std::vector<uint32_t> 
 }
 
 size_t t2mo_layout(T2moDev &d, void *base) {
-  size_t at = 0;
-  auto take = [&](auto *&ptr, size_t count) {
-    using E = std::remove_reference_t<decltype(*ptr)>;
-    at = (at + 255) & ~(size_t)255;
-    ptr = base ? (E *)((char *)base + at) : nullptr;
-    at += count * sizeof(E);
-  };
+  LayoutTaker take{base};
   const size_t G = (size_t)d.max_frames * d.P;
   take(d.pkt, d.P + 1);
   take(d.tq, G + 1);
   take(d.td, G + 1);
   take(d.crc, G);
   take(d.tab, T2MO_TAB_WORDS);
-  return at;
+  return take.at;
 }
 
 hipError_t t2mo_launch(const T2moDev &d, const T2moRun &r, hipStream_t st) {

@@ -1,127 +1,56 @@
 // ULE encapsulation (RFC 4326) on gfx950: a device buffer of PDUs and an offset table -> 188-byte TS packets.
 // Semantics: include/dvbt2ll_hip.h; tests/ule_ref.py is the sequential restatement every output is compared with.
 //
-// With packing, the Payload Pointer byte makes a packet's capacity depend on whether an SNDU starts in it, so where an
-// SNDU lands depends on every SNDU before it through a small state: q, the payload bytes used in the open PUSI packet
-// (0: none open; otherwise 2 .. 182, since a packet with fewer than two free bytes is closed).  An SNDU of n bytes maps
-// (q, packets completed) to (q', packets completed'), and such maps compose, so the positions come from a scan over
-// maps.  Passes of one run, all on the caller's stream:
+// The units ts_section_packer.h packs are the SNDUs: a packet with fewer than two free bytes is closed, since an SNDU's
+// Length field must fit (MINFREE 2).  Passes of one run, all on the caller's stream:
 //   measure    one lane per PDU: validity, Type, SNDU length n (packing 0: its packet count, for the sum scan)
-//   maps       packing 1: one workgroup per tile of ULE_TILE PDUs; lane q walks the tile from entry state q and
-//              stores (packets completed << 8 | exit state)
-//   compose    packing 1: one workgroup; ST_ROUND tile maps at a time are composed by a Hillis-Steele scan in LDS and
-//              applied to the running (state, packets), which is carried from round to round: each tile's entry
-//   walk       packing 1: one workgroup per tile walks it from its entry: per PDU its first packet and payload offset
-//   sum scan   packing 0: every SNDU starts a packet, so the first packets are an exclusive sum (three launches)
-//   crc        SNDUs of up to CRC_LANE_MAX bytes a lane each; the longer ones (listed by measure) a wavefront each:
-//              lanes take contiguous chunks through the byte table and the chunks are joined with x^(8 n) mod G
-//   emit       one workgroup per EMIT_PKTS output packets: a lane per packet finds what the packet begins with (a
-//              search in the per-PDU first packets) into LDS, then a lane per 16 output bytes gathers header / PP /
-//              SNDU header / PDU / CRC / FF and stores a head up to the first 16-byte boundary, then uint4s
+//   maps, compose, walk   packing 1: the packer's state scan
+//   sum scan   packing 0: every SNDU starts a packet, so the first packets are an exclusive sum (dev_scan.h)
+//   crc        SNDUs of up to CRC_LANE_MAX bytes a lane each; the longer ones (listed by measure) a wavefront each
+//              (crc32_mpeg2.h)
+//   emit       this file's own, of the shape ts_section_packer.h describes: with the shared emit body ule_emit's code
+//              came out differently placed and the call measured 0.6 % slower, so ULE keeps the code it had
 //   count      the resume position, and the counters of the PDUs before it
 // The cut (the determined packets that capacity allows, the flush packet) is arithmetic on the scan's totals: emit
 // and count each work it out for themselves.
 #include "ule_kernels.h"
 
 #include <algorithm>
-#include <type_traits>
+
+#include "crc32_mpeg2.h"
+#include "dev_scan.h"
+#include "host_util.h"
+#include "ts_section_packer.h"
 
 namespace t2 {
 
 namespace {
 
-constexpr uint32_t ULE_POLY = 0x04C11DB7u;
-enum : uint32_t { U_LEN = 0xFFFFu, U_SKIP_TYPE = 1u << 30, U_SKIP_LEN = 1u << 31 };
+enum : uint32_t { U_LEN = PK_LEN, U_SKIP_TYPE = 1u << 30, U_SKIP_LEN = 1u << 31 };
 enum : int { C_T = 0, C_Q = 1, C_S = 2, C_NLONG = 3 };   // d.ctl
-constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 4, SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
-constexpr int ST_Q = ULE_MAP_STATES, ST_TILE = ULE_TILE, ST_ROUND = 32, ST_THREADS = 512;
-constexpr int ST_PER = (ST_ROUND * ST_Q + ST_THREADS - 1) / ST_THREADS;   // map entries of a round per compose lane
+static_assert(ULE_MAP_STATES == PK_STATES && ULE_TILE == PK_TILE, "the layout is sized for the packer's maps");
+constexpr int MINFREE = 2;
 constexpr uint32_t CRC_LANE_MAX = 192;
-constexpr uint32_t EMIT_PKTS = 64;
 constexpr uint32_t COUNT_BLOCKS = 64;   // the count pass strides over the PDUs past COUNT_BLOCKS x 256
 
-// ------------------------------------------------------------------------------------------ device-wide sum scan
-// (the three-launch structure of modeadapt_kernels.hip: tile sums of 1024, one workgroup over the sums, apply)
-__device__ uint32_t block_exclusive(uint32_t v, uint32_t *lds, uint32_t &total) {
-  const int t = threadIdx.x;
-  uint32_t *a = lds, *b = lds + SCAN_THREADS;
-  a[t] = v;
-  __syncthreads();
-  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-    uint32_t x = a[t];
-    if (t >= d) x = a[t - d] + x;
-    b[t] = x;
-    __syncthreads();
-    uint32_t *s = a; a = b; b = s;
-  }
-  total = a[SCAN_THREADS - 1];
-  const uint32_t ex = t ? a[t - 1] : 0;
-  __syncthreads();
-  return ex;
-}
-
-__global__ __launch_bounds__(SCAN_THREADS) void ule_scan_reduce(const uint32_t *in, uint32_t *tile, uint32_t n) {
+__global__ __launch_bounds__(SCAN_THREADS) void ule_scan_reduce(const uint32_t *in, uint32_t *tile, uint32_t n,
+                                                                const uint32_t *n_dev) {
   __shared__ uint32_t lds[SCAN_THREADS];
-  const uint32_t i0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  uint32_t s = 0;
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++)
-    if (i0 + q < n) s += in[i0 + q];
-  lds[threadIdx.x] = s;
-  __syncthreads();
-  for (int dd = SCAN_THREADS / 2; dd > 0; dd >>= 1) {
-    if ((int)threadIdx.x < dd) lds[threadIdx.x] += lds[threadIdx.x + dd];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) tile[blockIdx.x] = lds[0];
+  scan_reduce_body(in, tile, n, n_dev, lds);
 }
-
-// one workgroup: tile sums -> exclusive tile offsets in place, the grand total to tile[ntiles].  The second round
-// (tiles 256 and up) begins at the loop's second pass, with the tiles before it in carry.
 __global__ __launch_bounds__(SCAN_THREADS) void ule_scan_tiles(uint32_t *tile, uint32_t ntiles) {
   __shared__ uint32_t lds[2 * SCAN_THREADS];
-  uint32_t carry = 0;
-  for (uint32_t b = 0; b < ntiles; b += SCAN_THREADS) {
-    const uint32_t i = b + threadIdx.x;
-    const uint32_t v = i < ntiles ? tile[i] : 0;
-    uint32_t total;
-    const uint32_t ex = block_exclusive(v, lds, total);
-    if (i < ntiles) tile[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) tile[ntiles] = carry;
+  scan_tiles_body(tile, ntiles, lds);
 }
-
-__global__ __launch_bounds__(SCAN_THREADS) void ule_scan_apply(uint32_t *data, const uint32_t *tile, uint32_t n) {
+__global__ __launch_bounds__(SCAN_THREADS) void ule_scan_apply(uint32_t *data, const uint32_t *tile, uint32_t n,
+                                                               const uint32_t *n_dev) {
   __shared__ uint32_t lds[2 * SCAN_THREADS];
-  if (blockIdx.x * SCAN_TILE >= n) return;
-  const uint32_t i0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  uint32_t v[SCAN_ITEMS];
-  uint32_t s = 0;
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++) {
-    v[q] = i0 + q < n ? data[i0 + q] : 0;
-    s += v[q];
-  }
-  uint32_t total;
-  uint32_t run = tile[blockIdx.x] + block_exclusive(s, lds, total);
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; q++) {
-    if (i0 + q < n) data[i0 + q] = run;
-    run += v[q];
-  }
+  scan_apply_body(data, tile, n, n_dev, lds);
 }
+constexpr ScanKernels<uint32_t> ULE_SCAN{ule_scan_reduce, ule_scan_tiles, ule_scan_apply};
 
-uint32_t scan_tiles_of(uint32_t n) { return std::max<uint32_t>(1, (n + SCAN_TILE - 1) / SCAN_TILE); }
-uint32_t state_tiles_of(uint32_t n) { return std::max<uint32_t>(1, (n + ST_TILE - 1) / ST_TILE); }
-
-hipError_t scan_exclusive(uint32_t *data, uint32_t *tile, uint32_t n, hipStream_t st) {
-  const uint32_t ntiles = scan_tiles_of(n);
-  hipLaunchKernelGGL(ule_scan_reduce, dim3(ntiles), dim3(SCAN_THREADS), 0, st, data, tile, n);
-  hipLaunchKernelGGL(ule_scan_tiles, dim3(1), dim3(SCAN_THREADS), 0, st, tile, ntiles);
-  hipLaunchKernelGGL(ule_scan_apply, dim3(ntiles), dim3(SCAN_THREADS), 0, st, data, tile, n);
-  return hipGetLastError();
-}
+uint32_t state_tiles_of(uint32_t n) { return std::max<uint32_t>(1, (n + PK_TILE - 1) / PK_TILE); }
+__device__ inline PkUnits ule_units(const UleDev &d, uint32_t N) { return PkUnits{d.len, d.pkt, d.at, N}; }
 
 // ------------------------------------------------------------------------------------------ measure
 __global__ __launch_bounds__(256) void ule_measure(UleDev d, UleRun r) {
@@ -168,139 +97,16 @@ __global__ __launch_bounds__(256) void ule_measure(UleDev d, UleRun r) {
 }
 
 // ------------------------------------------------------------------------------------------ the state scan
-// one SNDU of n bytes (0: a skipped PDU) entered in state q with pk packets completed; cont: it continues an earlier
-// call's SNDU, which begins a packet without a Payload Pointer
-__device__ inline void ule_step(uint32_t n, bool cont, uint32_t &q, uint32_t &pk) {
-  if (!n) return;
-  uint32_t rem = n;
-  if (!cont) {
-    const uint32_t a = q ? q : 1, space = 184 - a;
-    if (n <= space) {
-      const uint32_t e = a + n;
-      if (e >= 183) { pk++; q = 0; }   // the last byte, or one free byte (FF): the packet is closed
-      else q = e;
-      return;
-    }
-    pk++;
-    rem = n - space;
-  }
-  pk += rem / 184;
-  rem %= 184;
-  if (rem == 0) q = 0;
-  else if (rem >= 182) { pk++; q = 0; }   // 183 + FF, 182 + FF FF
-  else q = 1 + rem;                       // PUSI, PP = rem: the next SNDU starts behind it
+__global__ __launch_bounds__(PK_THREADS) void ule_maps(UleDev d, uint32_t N) {
+  pk_maps_body<MINFREE>(d.len, N, d.ctl[C_S], true, d.maps);
 }
 
-// the tile's SNDU lengths into LDS; the first of the call less the bytes an earlier call emitted
-__device__ inline void ule_tile_lens(const UleDev &d, uint32_t N, uint32_t base, uint32_t s, uint16_t *ln) {
-  for (uint32_t k = threadIdx.x; k < (uint32_t)ST_TILE; k += blockDim.x) {
-    const uint32_t i = base + k;
-    uint32_t v = i < N ? d.len[i] & U_LEN : 0;
-    if (i == 0 && v) v -= s;
-    ln[k] = (uint16_t)v;
-  }
-  __syncthreads();
+__global__ __launch_bounds__(PK_COMPOSE_THREADS) void ule_compose(UleDev d, uint32_t ntiles) {
+  pk_compose_body(d.maps, ntiles, d.ent_q, d.ent_pk, &d.ctl[C_T], &d.ctl[C_Q]);
 }
 
-__global__ __launch_bounds__(256) void ule_maps(UleDev d, uint32_t N) {
-  __shared__ uint16_t ln[ST_TILE];
-  const uint32_t s = d.ctl[C_S], base = blockIdx.x * ST_TILE;
-  ule_tile_lens(d, N, base, s, ln);
-  if (threadIdx.x >= (uint32_t)ST_Q) return;
-  uint32_t q = threadIdx.x, pk = 0;
-  ule_step(ln[0], s != 0 && base == 0, q, pk);
-  for (int k = 1; k < ST_TILE; k++) ule_step(ln[k], false, q, pk);
-  d.maps[(size_t)blockIdx.x * ST_Q + threadIdx.x] = (pk << 8) | q;
-}
-
-__global__ __launch_bounds__(ST_THREADS) void ule_compose(UleDev d, uint32_t ntiles) {
-  __shared__ uint32_t buf[2][ST_ROUND * ST_Q];
-  const uint32_t total = ntiles * ST_Q;
-  uint32_t cq = 0, cpk = 0;   // the running state: entered the round with
-  uint32_t nxt[ST_PER];
-#pragma unroll
-  for (int k = 0; k < ST_PER; k++) {
-    const uint32_t e = threadIdx.x + k * ST_THREADS;
-    nxt[k] = e < total ? d.maps[e] : e % ST_Q;
-  }
-  // the second round (tiles ST_ROUND and up) begins at this loop's second pass: cq / cpk then hold the state and the
-  // packets after the tiles before it, and the round's maps were fetched during the round before
-  for (uint32_t b = 0; b < ntiles; b += ST_ROUND) {
-    uint32_t *A = buf[0], *B = buf[1];
-#pragma unroll
-    for (int k = 0; k < ST_PER; k++) {
-      const uint32_t e = threadIdx.x + k * ST_THREADS;
-      if (e < (uint32_t)(ST_ROUND * ST_Q)) A[e] = nxt[k];
-    }
-    if (b + ST_ROUND < ntiles) {
-#pragma unroll
-      for (int k = 0; k < ST_PER; k++) {
-        const uint32_t e = threadIdx.x + k * ST_THREADS, g = (b + ST_ROUND) * ST_Q + e;
-        nxt[k] = g < total ? d.maps[g] : e % ST_Q;   // past the last tile: the identity
-      }
-    }
-    __syncthreads();
-    // inclusive scan over the round's tiles: A[t] becomes tiles b .. b + t composed in order
-    for (int dd = 1; dd < ST_ROUND; dd <<= 1) {
-#pragma unroll
-      for (int k = 0; k < ST_PER; k++) {
-        const uint32_t e = threadIdx.x + k * ST_THREADS;
-        if (e < (uint32_t)(ST_ROUND * ST_Q)) {
-          const uint32_t t = e / ST_Q;
-          uint32_t v = A[e];
-          if (t >= (uint32_t)dd) {
-            const uint32_t f = A[e - dd * ST_Q];               // the tiles before, from this entry state
-            v = (f & ~255u) + A[t * ST_Q + (f & 255u)];        // then these, from the state those leave
-          }
-          B[e] = v;
-        }
-      }
-      __syncthreads();
-      uint32_t *x = A; A = B; B = x;
-    }
-    const uint32_t t = threadIdx.x;
-    if (t < (uint32_t)ST_ROUND && b + t < ntiles) {
-      uint32_t eq = cq, epk = cpk;
-      if (t) {
-        const uint32_t f = A[(t - 1) * ST_Q + cq];
-        eq = f & 255u;
-        epk = cpk + (f >> 8);
-      }
-      d.ent_q[b + t] = eq;
-      d.ent_pk[b + t] = epk;
-    }
-    const uint32_t f = A[(ST_ROUND - 1) * ST_Q + cq];
-    cq = f & 255u;
-    cpk += f >> 8;
-    __syncthreads();   // the next round overwrites the buffers
-  }
-  if (threadIdx.x == 0) {
-    d.ctl[C_T] = cpk;
-    d.ctl[C_Q] = cq;
-  }
-}
-
-__global__ __launch_bounds__(256) void ule_walk(UleDev d, uint32_t N) {
-  __shared__ uint16_t ln[ST_TILE];
-  __shared__ uint32_t pk_s[ST_TILE];
-  __shared__ uint8_t at_s[ST_TILE];
-  const uint32_t s = d.ctl[C_S], base = blockIdx.x * ST_TILE;
-  ule_tile_lens(d, N, base, s, ln);
-  if (threadIdx.x == 0) {
-    uint32_t q = d.ent_q[blockIdx.x], pk = d.ent_pk[blockIdx.x];
-    for (int k = 0; k < ST_TILE; k++) {
-      const bool cont = k == 0 && base == 0 && s != 0;
-      pk_s[k] = pk;
-      at_s[k] = (uint8_t)(cont ? 0 : q ? q : 1);
-      ule_step(ln[k], cont, q, pk);
-    }
-  }
-  __syncthreads();
-  for (uint32_t k = threadIdx.x; k < (uint32_t)ST_TILE; k += 256)
-    if (base + k < N) {
-      d.pkt[base + k] = pk_s[k];
-      d.at[base + k] = at_s[k];
-    }
+__global__ __launch_bounds__(PK_THREADS) void ule_walk(UleDev d, uint32_t N) {
+  pk_walk_body<MINFREE>(ule_units(d, N), d.ctl[C_S], true, d.ent_q, d.ent_pk);
 }
 
 // ------------------------------------------------------------------------------------------ SNDU bytes
@@ -342,42 +148,12 @@ __device__ inline uint32_t ule_sndu_word(const UleDev &d, const UleRun &r, uint3
 }
 
 // ------------------------------------------------------------------------------------------ CRC-32
-__device__ inline uint32_t gf_mul(uint32_t a, uint32_t b) {   // a(x) b(x) mod G, bit 31 = x^31
-  uint32_t r = 0;
-  for (int i = 31; i >= 0; i--) {
-    r = (r << 1) ^ ((r >> 31) ? ULE_POLY : 0u);
-    if ((b >> i) & 1) r ^= a;
-  }
-  return r;
-}
-
-__device__ inline uint32_t crc_byte(uint32_t crc, uint32_t b, const uint32_t *tab) {
-  return (crc << 8) ^ tab[(crc >> 24) ^ b];
-}
-
-// n bytes at p, all inside one PDU: bytes up to a 4-byte boundary, aligned words, the rest
-__device__ inline uint32_t crc_run(uint32_t crc, const uint8_t *p, uint32_t n, const uint32_t *tab) {
-  while (n && ((uintptr_t)p & 3)) {
-    crc = crc_byte(crc, *p++, tab);
-    n--;
-  }
-  for (; n >= 4; n -= 4, p += 4) {
-    const uint32_t w = *(const uint32_t *)p;
-    crc = crc_byte(crc, w & 255, tab);
-    crc = crc_byte(crc, (w >> 8) & 255, tab);
-    crc = crc_byte(crc, (w >> 16) & 255, tab);
-    crc = crc_byte(crc, w >> 24, tab);
-  }
-  for (; n; n--) crc = crc_byte(crc, *p++, tab);
-  return crc;
-}
-
 // SNDU bytes [lo, hi) of an SNDU (hi <= n - 4): the header's, then the PDU's
 __device__ inline uint32_t crc_span(const UleDev &d, uint32_t crc, uint32_t n, uint32_t type, const uint8_t *pdu,
                                     uint32_t lo, uint32_t hi, const uint32_t *tab) {
   const uint32_t hl = d.d_bit ? 4 : 10;
-  for (; lo < hi && lo < hl; lo++) crc = crc_byte(crc, ule_header_byte(d, n, type, lo), tab);
-  if (lo < hi) crc = crc_run(crc, pdu + (lo - hl), hi - lo, tab);
+  for (; lo < hi && lo < hl; lo++) crc = crc32m_byte(crc, ule_header_byte(d, n, type, lo), tab);
+  if (lo < hi) crc = crc32m_run(crc, pdu + (lo - hl), hi - lo, tab);
   return crc;
 }
 
@@ -405,20 +181,12 @@ __global__ __launch_bounds__(256) void ule_crc_long(UleDev d, UleRun r) {
     if (j >= r.n) continue;
     const uint32_t nj = d.len[j] & U_LEN, tj = d.typ[j], oj = r.off[r.i0 + j];
     if (nj <= CRC_LANE_MAX) continue;
-    // the T bytes are padded in front to 64 chunks of c bytes: leading zeros leave a zero register unchanged, so every
-    // lane's chunk has the same length and the tree multiplies by x^(8 c 2^m) at level m; the initial 0xFFFFFFFF is
-    // added as 0xFFFFFFFF x^(8 T)
-    const uint32_t T = nj - 4, c = (T + 63) >> 6, pad = 64 * c - T;
-    int lo = (int)(lane * c) - (int)pad, hi = lo + (int)c;
-    if (lo < 0) lo = 0;
+    const uint32_t T = nj - 4;
+    int lo, hi;
+    const uint32_t c = crc32m_wave_chunk(lane, T, lo, hi);
     uint32_t crc = 0;
     if (hi > lo) crc = crc_span(d, 0, nj, tj, r.pdu + oj, (uint32_t)lo, (uint32_t)hi, tab);
-    for (int lv = 0; lv < 6; lv++) {
-      const uint32_t other = __shfl_xor(crc, 1 << lv);
-      const bool right = (lane >> lv) & 1;
-      crc = gf_mul(right ? other : crc, xp[c << lv]) ^ (right ? crc : other);
-    }
-    crc ^= gf_mul(0xFFFFFFFFu, xp[T]);
+    crc = crc32m_wave_join(crc, lane, c, T, xp);
     if (lane == 0) d.crc[j] = crc;
   }
 }
@@ -558,14 +326,14 @@ __device__ inline uint32_t ule_out_word(const UleDev &d, const UleRun &r, const 
 }
 
 // The grid covers the packets that PDUs lying side by side can become (ule_packet_estimate); where the offsets make
-// valid PDUs overlap and the packets are more, a workgroup takes more than one group of EMIT_PKTS: its second trip
+// valid PDUs overlap and the packets are more, a workgroup takes more than one group of PK_EMIT_PKTS: its second trip
 // begins at the loop's second pass
 __global__ __launch_bounds__(256) void ule_emit(UleDev d, UleRun r, const uint32_t *total) {
-  __shared__ UleRec rec[EMIT_PKTS];
+  __shared__ UleRec rec[PK_EMIT_PKTS];
   __shared__ uint32_t cnt[2];
   const UleCut c = ule_cut(d, r, total);
-  for (uint32_t p0 = blockIdx.x * EMIT_PKTS; p0 < c.E; p0 += gridDim.x * EMIT_PKTS) {
-    const uint32_t np = c.E - p0 < EMIT_PKTS ? c.E - p0 : EMIT_PKTS;
+  for (uint32_t p0 = blockIdx.x * PK_EMIT_PKTS; p0 < c.E; p0 += gridDim.x * PK_EMIT_PKTS) {
+    const uint32_t np = c.E - p0 < PK_EMIT_PKTS ? c.E - p0 : PK_EMIT_PKTS;
     if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
     __syncthreads();   // the trip before no longer reads rec
     if (threadIdx.x < np) {
@@ -649,26 +417,11 @@ __global__ __launch_bounds__(256) void ule_count(UleDev d, UleRun r, const uint3
 }  // namespace
 
 void ule_host_tables(uint32_t *tab) {
-  for (uint32_t v = 0; v < 256; v++) {
-    uint32_t c = v << 24;
-    for (int i = 0; i < 8; i++) c = (c << 1) ^ ((c >> 31) ? ULE_POLY : 0u);
-    tab[v] = c;
-  }
-  uint32_t p = 1;   // x^(8 n) mod G
-  for (int n = 0; n <= ULE_MAX_SNDU; n++) {
-    tab[256 + n] = p;
-    p = (p << 8) ^ tab[p >> 24];
-  }
+  crc32m_host_tables(tab, ULE_MAX_SNDU + 1);
 }
 
 size_t ule_layout(UleDev &d, void *base) {
-  size_t at = 0;
-  auto take = [&](auto *&ptr, size_t count) {
-    using E = std::remove_reference_t<decltype(*ptr)>;
-    at = (at + 255) & ~(size_t)255;
-    ptr = base ? (E *)((char *)base + at) : nullptr;
-    at += count * sizeof(E);
-  };
+  LayoutTaker take{base};
   const size_t n = std::max<uint32_t>(d.max_pdus, 1), nt = state_tiles_of(d.max_pdus);
   take(d.res, ULE_R_WORDS + 2);
   d.ctl = base ? (uint32_t *)(d.res + ULE_R_WORDS) : nullptr;
@@ -679,11 +432,11 @@ size_t ule_layout(UleDev &d, void *base) {
   take(d.pkt, n);
   take(d.at, n);
   take(d.tile, scan_tiles_of(d.max_pdus) + 1);
-  take(d.maps, nt * ST_Q);
+  take(d.maps, nt * PK_STATES);
   take(d.ent_q, nt);
   take(d.ent_pk, nt);
   take(d.tab, ULE_TAB_WORDS);
-  return at;
+  return take.at;
 }
 
 uint64_t ule_packet_estimate(const UleDev &d, uint64_t pdu_len, uint64_t n) {
@@ -705,11 +458,11 @@ hipError_t ule_launch(const UleDev &d, const UleRun &r, hipStream_t st) {
   const uint32_t *total = d.ctl + C_T;
   hipLaunchKernelGGL(ule_measure, dim3(nb), dim3(256), 0, st, d, r);
   if (d.packing) {
-    hipLaunchKernelGGL(ule_maps, dim3(nt), dim3(256), 0, st, d, r.n);
-    hipLaunchKernelGGL(ule_compose, dim3(1), dim3(ST_THREADS), 0, st, d, nt);
-    hipLaunchKernelGGL(ule_walk, dim3(nt), dim3(256), 0, st, d, r.n);
+    hipLaunchKernelGGL(ule_maps, dim3(nt), dim3(PK_THREADS), 0, st, d, r.n);
+    hipLaunchKernelGGL(ule_compose, dim3(1), dim3(PK_COMPOSE_THREADS), 0, st, d, nt);
+    hipLaunchKernelGGL(ule_walk, dim3(nt), dim3(PK_THREADS), 0, st, d, r.n);
   } else {
-    if ((e = scan_exclusive(d.pkt, d.tile, r.n, st)) != hipSuccess) return e;
+    if ((e = scan_exclusive(ULE_SCAN, d.pkt, d.tile, r.n, nullptr, st)) != hipSuccess) return e;
     total = d.tile + scan_tiles_of(r.n);
   }
   hipLaunchKernelGGL(ule_crc_short, dim3(nb), dim3(256), 0, st, d, r);
@@ -718,7 +471,7 @@ hipError_t ule_launch(const UleDev &d, const UleRun &r, hipStream_t st) {
   if (nlong) hipLaunchKernelGGL(ule_crc_long, dim3((nlong + 3) / 4), dim3(256), 0, st, d, r);
   // emit's grid is sized for PDUs that lie side by side and strides where overlapping ones make more packets
   const uint64_t est = std::min<uint64_t>(r.cap, ule_packet_estimate(d, r.pdu_len, r.n));
-  if (r.cap) hipLaunchKernelGGL(ule_emit, dim3((uint32_t)((est + EMIT_PKTS - 1) / EMIT_PKTS)), dim3(256), 0, st, d, r, total);
+  if (r.cap) hipLaunchKernelGGL(ule_emit, dim3((uint32_t)((est + PK_EMIT_PKTS - 1) / PK_EMIT_PKTS)), dim3(256), 0, st, d, r, total);
   hipLaunchKernelGGL(ule_count, dim3(std::min(COUNT_BLOCKS, nb)), dim3(256), 0, st, d, r, total);
   return hipGetLastError();
 }
