@@ -75,6 +75,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -550,176 +551,181 @@ int run_tsnpd(dvbt2ll_chain *h, const std::string &in_path, const std::string &o
 
 constexpr int kInputUle = 4;   // --input ule (the chain itself runs in DVBT2LL_INPUT_TS)
 
-// --input ule: the file's length-prefixed PDUs -> the ULE encapsulator in chunks -> a temporary TS file, which the
-// caller reads as it reads a TS file.  Returns the file rewound, or nullptr.
+constexpr size_t kEncapChunk = 4 << 20, kEncapMaxPdus = 65536;   // PDU bytes and PDUs per encapsulator call
+
+// What one of --input ule, mpe, mpe-fec and gse gives encap_file: its names in the stderr lines, its output unit, and
+// its calls.  The callables hold the handle, the position carried from call to call and the counter totals.
+struct Encap {
+  const char *name, *unit;   // "ule", "packet"
+  size_t unit_bytes;         // of an output unit: a TS packet, a BBFRAME
+  bool more_at_eof;          // a flushed call can stop short of the last PDU (MPE-FEC's max_frames) and is continued
+  // the capacity in units that holds n records of `bytes` bytes lying side by side
+  std::function<int64_t(int64_t bytes, int64_t n)> bound;
+  // one run_host call from the carried position: adds its counters to the totals, carries the position on, says how
+  // many units it wrote and which PDU it resumes at
+  std::function<int(const uint8_t *pdu, int64_t bytes, const uint32_t *off, int64_t n, uint8_t *out, int64_t cap,
+                    bool flush, int64_t *units, int64_t *resume_pdu)> run;
+  std::function<void()> report;   // the line of counter totals
+};
+
+// The file's length-prefixed PDUs -> an encapsulator in chunks, each call continuing from the previous one's resume
+// position, flushed at the end of the file -> a temporary file of its output units, which the caller reads as it reads
+// a TS or BBFRAME file.  Returns the file rewound, or nullptr.
+FILE *encap_file(const Encap &b, const std::string &in_path) {
+  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
+  FILE *tmp = std::tmpfile();
+  if (!fin || !tmp) {
+    std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : "a temporary file", std::strerror(errno));
+    return nullptr;
+  }
+  std::vector<uint8_t> pdus, out;
+  std::vector<uint32_t> off(1, 0);
+  bool eof = false;
+  int st = 0;
+  while (!st) {
+    while (!eof && pdus.size() < kEncapChunk && off.size() <= kEncapMaxPdus) {
+      uint8_t lb[2];
+      if (std::fread(lb, 1, 2, fin) != 2) { eof = true; break; }
+      const size_t len = ((size_t)lb[0] << 8) | lb[1], old = pdus.size();
+      pdus.resize(old + len);
+      if (len && std::fread(pdus.data() + old, 1, len, fin) != len) { pdus.resize(old); eof = true; break; }   // a cut record
+      off.push_back((uint32_t)pdus.size());
+    }
+    const int64_t n = (int64_t)off.size() - 1;
+    const int64_t cap = b.bound((int64_t)pdus.size(), n);
+    out.resize((size_t)cap * b.unit_bytes);
+    const uint8_t none = 0;
+    int64_t units = 0, resume_pdu = 0;
+    if ((st = b.run(pdus.empty() ? &none : pdus.data(), (int64_t)pdus.size(), off.data(), n, out.data(), cap, eof, &units,
+                    &resume_pdu)))
+      break;
+    if (units && std::fwrite(out.data(), b.unit_bytes, (size_t)units, tmp) != (size_t)units) { st = -1; break; }
+    // continue from the resume position: drop the PDUs before it
+    const uint32_t cut = off[(size_t)resume_pdu];
+    pdus.erase(pdus.begin(), pdus.begin() + cut);
+    off.erase(off.begin(), off.begin() + (size_t)resume_pdu);
+    for (uint32_t &o : off) o -= cut;
+    const bool stuck = resume_pdu == 0 && units == 0;
+    if (eof && (!b.more_at_eof || off.size() == 1 || stuck)) break;
+    // nothing consumed and no room to read on (a short datagram with max_pdus skipped records behind it holds its
+    // open packet or frame back for ever): give up, not loop
+    if (stuck && (pdus.size() >= kEncapChunk || off.size() > kEncapMaxPdus)) {
+      std::fprintf(stderr, "dvbt2ll_tx: %s: no %s completes within %zu bytes / %zu records\n", b.name, b.unit, pdus.size(),
+                   off.size() - 1);
+      st = -1;
+      break;
+    }
+  }
+  if (st) std::fprintf(stderr, "dvbt2ll_tx: %s run failed: %s\n", b.name, dvbt2ll_strerror(st));
+  b.report();
+  if (fin != stdin) std::fclose(fin);
+  if (st) { std::fclose(tmp); return nullptr; }
+  std::rewind(tmp);
+  return tmp;
+}
+
+// --input ule: the ULE encapsulator's TS packets (encap_file)
 FILE *run_ule(const std::string &in_path, int pid, int d_bit, const uint8_t *dest, int packing, int device) {
-  const size_t chunk = 4 << 20, max_pdus = 65536;   // PDU bytes and PDUs per encapsulator call
   dvbt2ll_ule_params up;
   std::memset(&up, 0, sizeof(up));
   up.pid = pid;
   up.d_bit = d_bit;
   std::memcpy(up.dest, dest, 6);
   up.packing = packing;
-  up.max_pdu_bytes = (int64_t)chunk + 65536;
-  up.max_pdus = (int)max_pdus;
+  up.max_pdu_bytes = (int64_t)kEncapChunk + 65536;
+  up.max_pdus = (int)kEncapMaxPdus;
   dvbt2ll_ule *enc = nullptr;
   int st = dvbt2ll_ule_create(&up, device, &enc);
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: ule: %s\n", dvbt2ll_strerror(st)); return nullptr; }
-  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
-  FILE *ts = std::tmpfile();
-  if (!fin || !ts) {
-    std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : "a temporary file", std::strerror(errno));
-    dvbt2ll_ule_destroy(enc);
-    return nullptr;
-  }
-  std::vector<uint8_t> pdus, out;
-  std::vector<uint32_t> off(1, 0);
   dvbt2ll_ule_pos pos = {0, 0, 0};
   dvbt2ll_ule_result tot;
   std::memset(&tot, 0, sizeof(tot));
-  bool eof = false;
-  while (!st) {
-    while (!eof && pdus.size() < chunk && off.size() <= max_pdus) {
-      uint8_t lb[2];
-      if (std::fread(lb, 1, 2, fin) != 2) { eof = true; break; }
-      const size_t len = ((size_t)lb[0] << 8) | lb[1], old = pdus.size();
-      pdus.resize(old + len);
-      if (len && std::fread(pdus.data() + old, 1, len, fin) != len) { pdus.resize(old); eof = true; break; }   // a cut record
-      off.push_back((uint32_t)pdus.size());
-    }
-    const int64_t n = (int64_t)off.size() - 1;
-    // the records lie side by side in pdus, so this many packets hold them all
-    const int64_t cap = packing ? ((int64_t)pdus.size() + 14 * n) / 182 + 2 : ((int64_t)pdus.size() + 14 * n) / 184 + n + 1;
-    out.resize((size_t)cap * 188);
-    const uint8_t none = 0;
+  Encap b = {"ule", "packet", 188, false, nullptr, nullptr, nullptr};
+  b.bound = [&](int64_t bytes, int64_t n) {
+    return packing ? (bytes + 14 * n) / 182 + 2 : (bytes + 14 * n) / 184 + n + 1;
+  };
+  b.run = [&](const uint8_t *pdu, int64_t bytes, const uint32_t *off, int64_t n, uint8_t *out, int64_t cap, bool flush,
+              int64_t *units, int64_t *resume_pdu) {
     dvbt2ll_ule_result res;
-    if ((st = dvbt2ll_ule_run_host(enc, pdus.empty() ? &none : pdus.data(), (int64_t)pdus.size(), off.data(), nullptr, n,
-                                   &pos, out.data(), cap, eof, &res)))
-      break;
-    int64_t *a = &tot.pdus_in, *b = &res.pdus_in;
-    for (int i = 0; i < 8; i++) a[i] += b[i];
-    if (res.ts_packets && std::fwrite(out.data(), 188, (size_t)res.ts_packets, ts) != (size_t)res.ts_packets) { st = -1; break; }
-    // continue from the resume position: drop the PDUs before it
-    const uint32_t cut = off[(size_t)res.resume.pdu];
-    pdus.erase(pdus.begin(), pdus.begin() + cut);
-    off.erase(off.begin(), off.begin() + (size_t)res.resume.pdu);
-    for (uint32_t &o : off) o -= cut;
+    const int e = dvbt2ll_ule_run_host(enc, pdu, bytes, off, nullptr, n, &pos, out, cap, flush, &res);
+    if (e) return e;
+    int64_t *a = &tot.pdus_in, *c = &res.pdus_in;
+    for (int i = 0; i < 8; i++) a[i] += c[i];
     pos = {0, res.resume.sndu_byte, res.resume.cc};
-    if (eof) break;
-    // nothing consumed and no room to read on (a short datagram with max_pdus skipped records behind it holds its
-    // open packet back for ever): give up, not loop
-    if (res.resume.pdu == 0 && res.ts_packets == 0 && (pdus.size() >= chunk || off.size() > max_pdus)) {
-      std::fprintf(stderr, "dvbt2ll_tx: ule: no packet completes within %zu bytes / %zu records\n", pdus.size(), off.size() - 1);
-      st = -1;
-      break;
-    }
-  }
-  if (st) std::fprintf(stderr, "dvbt2ll_tx: ule run failed: %s\n", dvbt2ll_strerror(st));
-  std::fprintf(stderr, "dvbt2ll_tx: ule: pdus_in %lld, sndus %lld, skipped_len %lld, skipped_type %lld, ts_packets %lld, "
-               "pusi_packets %lld, pad_bytes %lld, flushed %lld\n", (long long)tot.pdus_in, (long long)tot.sndus,
-               (long long)tot.skipped_len, (long long)tot.skipped_type, (long long)tot.ts_packets,
-               (long long)tot.pusi_packets, (long long)tot.pad_bytes, (long long)tot.flushed);
-  if (fin != stdin) std::fclose(fin);
+    *units = res.ts_packets;
+    *resume_pdu = res.resume.pdu;
+    return 0;
+  };
+  b.report = [&] {
+    std::fprintf(stderr, "dvbt2ll_tx: ule: pdus_in %lld, sndus %lld, skipped_len %lld, skipped_type %lld, ts_packets %lld, "
+                 "pusi_packets %lld, pad_bytes %lld, flushed %lld\n", (long long)tot.pdus_in, (long long)tot.sndus,
+                 (long long)tot.skipped_len, (long long)tot.skipped_type, (long long)tot.ts_packets,
+                 (long long)tot.pusi_packets, (long long)tot.pad_bytes, (long long)tot.flushed);
+  };
+  FILE *ts = encap_file(b, in_path);
   dvbt2ll_ule_destroy(enc);
-  if (st) { std::fclose(ts); return nullptr; }
-  std::rewind(ts);
   return ts;
 }
 
 constexpr int kInputMpe = 6;   // --input mpe (the chain itself runs in DVBT2LL_INPUT_TS)
 
-// --input mpe: the file's length-prefixed PDUs -> the MPE encapsulator in chunks -> a temporary TS file, which the
-// caller reads as it reads a TS file.  Returns the file rewound, or nullptr.
+// --input mpe: the MPE encapsulator's TS packets (encap_file)
 FILE *run_mpe(const std::string &in_path, int pid, const uint8_t *mac, int mac_mode, int packing, int device) {
-  const size_t chunk = 4 << 20, max_pdus = 65536;   // PDU bytes and PDUs per encapsulator call
   dvbt2ll_mpe_params up;
   std::memset(&up, 0, sizeof(up));
   up.pid = pid;
   std::memcpy(up.mac, mac, 6);
   up.mac_mode = mac_mode;
   up.packing = packing;
-  up.max_pdu_bytes = (int64_t)chunk + 65536;
-  up.max_pdus = (int)max_pdus;
+  up.max_pdu_bytes = (int64_t)kEncapChunk + 65536;
+  up.max_pdus = (int)kEncapMaxPdus;
   dvbt2ll_mpe *enc = nullptr;
   int st = dvbt2ll_mpe_create(&up, device, &enc);
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: mpe: %s\n", dvbt2ll_strerror(st)); return nullptr; }
-  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
-  FILE *ts = std::tmpfile();
-  if (!fin || !ts) {
-    std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : "a temporary file", std::strerror(errno));
-    dvbt2ll_mpe_destroy(enc);
-    return nullptr;
-  }
-  std::vector<uint8_t> pdus, out;
-  std::vector<uint32_t> off(1, 0);
   dvbt2ll_mpe_pos pos = {0, 0, 0};
   dvbt2ll_mpe_result tot;
   std::memset(&tot, 0, sizeof(tot));
-  bool eof = false;
-  while (!st) {
-    while (!eof && pdus.size() < chunk && off.size() <= max_pdus) {
-      uint8_t lb[2];
-      if (std::fread(lb, 1, 2, fin) != 2) { eof = true; break; }
-      const size_t len = ((size_t)lb[0] << 8) | lb[1], old = pdus.size();
-      pdus.resize(old + len);
-      if (len && std::fread(pdus.data() + old, 1, len, fin) != len) { pdus.resize(old); eof = true; break; }   // a cut record
-      off.push_back((uint32_t)pdus.size());
-    }
-    const int64_t n = (int64_t)off.size() - 1;
-    // the records lie side by side in pdus, so this many packets hold them all
-    const int64_t cap = packing ? ((int64_t)pdus.size() + 16 * n) / 183 + 2 : ((int64_t)pdus.size() + 16 * n) / 184 + n + 1;
-    out.resize((size_t)cap * 188);
-    const uint8_t none = 0;
+  Encap b = {"mpe", "packet", 188, false, nullptr, nullptr, nullptr};
+  b.bound = [&](int64_t bytes, int64_t n) {
+    return packing ? (bytes + 16 * n) / 183 + 2 : (bytes + 16 * n) / 184 + n + 1;
+  };
+  b.run = [&](const uint8_t *pdu, int64_t bytes, const uint32_t *off, int64_t n, uint8_t *out, int64_t cap, bool flush,
+              int64_t *units, int64_t *resume_pdu) {
     dvbt2ll_mpe_result res;
-    if ((st = dvbt2ll_mpe_run_host(enc, pdus.empty() ? &none : pdus.data(), (int64_t)pdus.size(), off.data(), n,
-                                   &pos, out.data(), cap, eof, &res)))
-      break;
-    int64_t *a = &tot.pdus_in, *b = &res.pdus_in;
-    for (int i = 0; i < 9; i++) a[i] += b[i];
-    if (res.ts_packets && std::fwrite(out.data(), 188, (size_t)res.ts_packets, ts) != (size_t)res.ts_packets) { st = -1; break; }
-    // continue from the resume position: drop the PDUs before it
-    const uint32_t cut = off[(size_t)res.resume.pdu];
-    pdus.erase(pdus.begin(), pdus.begin() + cut);
-    off.erase(off.begin(), off.begin() + (size_t)res.resume.pdu);
-    for (uint32_t &o : off) o -= cut;
+    const int e = dvbt2ll_mpe_run_host(enc, pdu, bytes, off, n, &pos, out, cap, flush, &res);
+    if (e) return e;
+    int64_t *a = &tot.pdus_in, *c = &res.pdus_in;
+    for (int i = 0; i < 9; i++) a[i] += c[i];
     pos = {0, res.resume.section_byte, res.resume.cc};
-    if (eof) break;
-    // nothing consumed and no room to read on (a short datagram with max_pdus skipped records behind it holds its
-    // open packet back for ever): give up, not loop
-    if (res.resume.pdu == 0 && res.ts_packets == 0 && (pdus.size() >= chunk || off.size() > max_pdus)) {
-      std::fprintf(stderr, "dvbt2ll_tx: mpe: no packet completes within %zu bytes / %zu records\n", pdus.size(), off.size() - 1);
-      st = -1;
-      break;
-    }
-  }
-  if (st) std::fprintf(stderr, "dvbt2ll_tx: mpe run failed: %s\n", dvbt2ll_strerror(st));
-  std::fprintf(stderr, "dvbt2ll_tx: mpe: pdus_in %lld, sections %lld, skipped_len %lld, skipped_type %lld, mapped_macs %lld, "
-               "ts_packets %lld, pusi_packets %lld, pad_bytes %lld, flushed %lld\n", (long long)tot.pdus_in,
-               (long long)tot.sections, (long long)tot.skipped_len, (long long)tot.skipped_type,
-               (long long)tot.mapped_macs, (long long)tot.ts_packets, (long long)tot.pusi_packets,
-               (long long)tot.pad_bytes, (long long)tot.flushed);
-  if (fin != stdin) std::fclose(fin);
+    *units = res.ts_packets;
+    *resume_pdu = res.resume.pdu;
+    return 0;
+  };
+  b.report = [&] {
+    std::fprintf(stderr, "dvbt2ll_tx: mpe: pdus_in %lld, sections %lld, skipped_len %lld, skipped_type %lld, mapped_macs %lld, "
+                 "ts_packets %lld, pusi_packets %lld, pad_bytes %lld, flushed %lld\n", (long long)tot.pdus_in,
+                 (long long)tot.sections, (long long)tot.skipped_len, (long long)tot.skipped_type,
+                 (long long)tot.mapped_macs, (long long)tot.ts_packets, (long long)tot.pusi_packets,
+                 (long long)tot.pad_bytes, (long long)tot.flushed);
+  };
+  FILE *ts = encap_file(b, in_path);
   dvbt2ll_mpe_destroy(enc);
-  if (st) { std::fclose(ts); return nullptr; }
-  std::rewind(ts);
   return ts;
 }
 
 constexpr int kInputMpeFec = 7;   // --input mpe-fec (the chain itself runs in DVBT2LL_INPUT_TS)
 
-// --input mpe-fec: the file's length-prefixed PDUs -> the MPE-FEC encapsulator in chunks -> a temporary TS file, which
-// the caller reads as it reads a TS file.  Returns the file rewound, or nullptr.
+// --input mpe-fec: the MPE-FEC encapsulator's TS packets (encap_file)
 FILE *run_mpefec(const std::string &in_path, int pid, const uint8_t *mac, int mac_mode, int packing, int rows, int dcols,
                  int kcols, int device) {
-  const size_t chunk = 4 << 20, max_pdus = 65536;   // PDU bytes and PDUs per encapsulator call
   dvbt2ll_mpefec_params up;
   std::memset(&up, 0, sizeof(up));
   up.pid = pid;
   std::memcpy(up.mac, mac, 6);
   up.mac_mode = mac_mode;
   up.packing = packing;
-  up.max_pdu_bytes = (int64_t)chunk + 65536;
-  up.max_pdus = (int)max_pdus;
+  up.max_pdu_bytes = (int64_t)kEncapChunk + 65536;
+  up.max_pdus = (int)kEncapMaxPdus;
   up.rows = rows;
   up.data_columns = dcols;
   up.rs_columns = kcols;
@@ -727,40 +733,22 @@ FILE *run_mpefec(const std::string &in_path, int pid, const uint8_t *mac, int ma
   dvbt2ll_mpefec *enc = nullptr;
   int st = dvbt2ll_mpefec_create(&up, device, &enc);
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: mpe-fec: %s\n", dvbt2ll_strerror(st)); return nullptr; }
-  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
-  FILE *ts = std::tmpfile();
-  if (!fin || !ts) {
-    std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : "a temporary file", std::strerror(errno));
-    dvbt2ll_mpefec_destroy(enc);
-    return nullptr;
-  }
-  std::vector<uint8_t> pdus, out;
-  std::vector<uint32_t> off(1, 0);
   dvbt2ll_mpefec_pos pos = {0, 0, 0, 0, 0};
   dvbt2ll_mpefec_result tot;
   std::memset(&tot, 0, sizeof(tot));
-  bool eof = false;
-  while (!st) {
-    while (!eof && pdus.size() < chunk && off.size() <= max_pdus) {
-      uint8_t lb[2];
-      if (std::fread(lb, 1, 2, fin) != 2) { eof = true; break; }
-      const size_t len = ((size_t)lb[0] << 8) | lb[1], old = pdus.size();
-      pdus.resize(old + len);
-      if (len && std::fread(pdus.data() + old, 1, len, fin) != len) { pdus.resize(old); eof = true; break; }   // a cut record
-      off.push_back((uint32_t)pdus.size());
-    }
-    const int64_t n = (int64_t)off.size() - 1;
-    // the records lie side by side in pdus: two successive frames hold more than a table's bytes, which bounds the
-    // frames, and so this many packets hold all the sections
-    const int64_t fr = std::min<int64_t>(std::min<int64_t>(up.max_frames, n), 2 * (int64_t)pdus.size() / ((int64_t)dcols * rows + 1) + 2);
-    const int64_t bytes = (int64_t)pdus.size() + 16 * n + fr * kcols * (rows + 16);
-    const int64_t cap = packing ? bytes / 183 + 2 : bytes / 184 + n + fr * kcols + 1;
-    out.resize((size_t)cap * 188);
-    const uint8_t none = 0;
+  Encap b = {"mpe-fec", "packet", 188, true, nullptr, nullptr, nullptr};
+  // two successive frames hold more than a table's bytes, which bounds the frames, and so this many packets hold all
+  // the sections
+  b.bound = [&](int64_t bytes, int64_t n) {
+    const int64_t fr = std::min<int64_t>(std::min<int64_t>(up.max_frames, n), 2 * bytes / ((int64_t)dcols * rows + 1) + 2);
+    const int64_t all = bytes + 16 * n + fr * kcols * (rows + 16);
+    return packing ? all / 183 + 2 : all / 184 + n + fr * kcols + 1;
+  };
+  b.run = [&](const uint8_t *pdu, int64_t bytes, const uint32_t *off, int64_t n, uint8_t *out, int64_t cap, bool flush,
+              int64_t *units, int64_t *resume_pdu) {
     dvbt2ll_mpefec_result res;
-    if ((st = dvbt2ll_mpefec_run_host(enc, pdus.empty() ? &none : pdus.data(), (int64_t)pdus.size(), off.data(), n,
-                                      &pos, out.data(), cap, eof, &res)))
-      break;
+    const int e = dvbt2ll_mpefec_run_host(enc, pdu, bytes, off, n, &pos, out, cap, flush, &res);
+    if (e) return e;
     tot.pdus_in += res.pdus_in;
     tot.sections += res.sections;
     tot.fec_sections += res.fec_sections;
@@ -772,33 +760,21 @@ FILE *run_mpefec(const std::string &in_path, int pid, const uint8_t *mac, int ma
     tot.pusi_packets += res.pusi_packets;
     tot.pad_bytes += res.pad_bytes;
     tot.flushed = res.flushed;   // the last call's
-    if (res.ts_packets && std::fwrite(out.data(), 188, (size_t)res.ts_packets, ts) != (size_t)res.ts_packets) { st = -1; break; }
-    // continue from the resume position: drop the PDUs before it
-    const uint32_t cut = off[(size_t)res.resume.pdu];
-    pdus.erase(pdus.begin(), pdus.begin() + cut);
-    off.erase(off.begin(), off.begin() + (size_t)res.resume.pdu);
-    for (uint32_t &o : off) o -= cut;
-    const bool stuck = res.resume.pdu == 0 && res.ts_packets == 0;
     pos = res.resume;
     pos.pdu = 0;
-    if (eof && (off.size() == 1 || stuck)) break;
-    // nothing consumed and no room to read on: give up, not loop
-    if (stuck && (pdus.size() >= chunk || off.size() > max_pdus)) {
-      std::fprintf(stderr, "dvbt2ll_tx: mpe-fec: no packet completes within %zu bytes / %zu records\n", pdus.size(), off.size() - 1);
-      st = -1;
-      break;
-    }
-  }
-  if (st) std::fprintf(stderr, "dvbt2ll_tx: mpe-fec run failed: %s\n", dvbt2ll_strerror(st));
-  std::fprintf(stderr, "dvbt2ll_tx: mpe-fec: pdus_in %lld, sections %lld, fec_sections %lld, frames %lld, skipped_len %lld, "
-               "skipped_type %lld, mapped_macs %lld, ts_packets %lld, pusi_packets %lld, pad_bytes %lld, flushed %lld\n",
-               (long long)tot.pdus_in, (long long)tot.sections, (long long)tot.fec_sections, (long long)tot.frames,
-               (long long)tot.skipped_len, (long long)tot.skipped_type, (long long)tot.mapped_macs,
-               (long long)tot.ts_packets, (long long)tot.pusi_packets, (long long)tot.pad_bytes, (long long)tot.flushed);
-  if (fin != stdin) std::fclose(fin);
+    *units = res.ts_packets;
+    *resume_pdu = res.resume.pdu;
+    return 0;
+  };
+  b.report = [&] {
+    std::fprintf(stderr, "dvbt2ll_tx: mpe-fec: pdus_in %lld, sections %lld, fec_sections %lld, frames %lld, skipped_len %lld, "
+                 "skipped_type %lld, mapped_macs %lld, ts_packets %lld, pusi_packets %lld, pad_bytes %lld, flushed %lld\n",
+                 (long long)tot.pdus_in, (long long)tot.sections, (long long)tot.fec_sections, (long long)tot.frames,
+                 (long long)tot.skipped_len, (long long)tot.skipped_type, (long long)tot.mapped_macs,
+                 (long long)tot.ts_packets, (long long)tot.pusi_packets, (long long)tot.pad_bytes, (long long)tot.flushed);
+  };
+  FILE *ts = encap_file(b, in_path);
   dvbt2ll_mpefec_destroy(enc);
-  if (st) { std::fclose(ts); return nullptr; }
-  std::rewind(ts);
   return ts;
 }
 
@@ -957,79 +933,44 @@ FILE *run_mux(FILE *ts, const MuxOpt &m, int pid, int device) {
 
 constexpr int kInputGse = 5;   // --input gse (the chain itself runs in DVBT2LL_INPUT_BBFRAME)
 
-// --input gse: the file's length-prefixed PDUs -> the GSE encapsulator in chunks -> a temporary file of BBFRAMEs, which
-// the caller reads as it reads a BBFRAME file.  Returns the file rewound, or nullptr.
+// --input gse: the GSE encapsulator's BBFRAMEs (encap_file)
 FILE *run_gse(const dvbt2ll_chain *chain, const std::string &in_path, int label_len, const uint8_t *label, int device) {
-  const size_t chunk = 4 << 20, max_pdus = 65536;   // PDU bytes and PDUs per encapsulator call
   dvbt2ll_gse_params gp;
   std::memset(&gp, 0, sizeof(gp));
   int st = dvbt2ll_gse_params_from_chain(chain, 0, &gp);
   gp.label_len = label_len;
   std::memcpy(gp.label, label, 6);
-  gp.max_pdu_bytes = (int64_t)chunk + 65536;
-  gp.max_pdus = (int)max_pdus;
+  gp.max_pdu_bytes = (int64_t)kEncapChunk + 65536;
+  gp.max_pdus = (int)kEncapMaxPdus;
   dvbt2ll_gse *enc = nullptr;
   if (!st) st = dvbt2ll_gse_create(&gp, device, &enc);
   if (st) { std::fprintf(stderr, "dvbt2ll_tx: gse: %s\n", dvbt2ll_strerror(st)); return nullptr; }
   const int64_t Lb = gp.kbch / 8, D = Lb - 10;
-  FILE *fin = in_path == "-" ? stdin : std::fopen(in_path.c_str(), "rb");
-  FILE *bb = std::tmpfile();
-  if (!fin || !bb) {
-    std::fprintf(stderr, "dvbt2ll_tx: cannot open %s: %s\n", !fin ? in_path.c_str() : "a temporary file", std::strerror(errno));
-    dvbt2ll_gse_destroy(enc);
-    return nullptr;
-  }
-  std::vector<uint8_t> pdus, out;
-  std::vector<uint32_t> off(1, 0);
   dvbt2ll_gse_pos pos = {0, 0, 0};
   dvbt2ll_gse_result tot;
   std::memset(&tot, 0, sizeof(tot));
-  bool eof = false;
-  while (!st) {
-    while (!eof && pdus.size() < chunk && off.size() <= max_pdus) {
-      uint8_t lb[2];
-      if (std::fread(lb, 1, 2, fin) != 2) { eof = true; break; }
-      const size_t len = ((size_t)lb[0] << 8) | lb[1], old = pdus.size();
-      pdus.resize(old + len);
-      if (len && std::fread(pdus.data() + old, 1, len, fin) != len) { pdus.resize(old); eof = true; break; }   // a cut record
-      off.push_back((uint32_t)pdus.size());
-    }
-    const int64_t n = (int64_t)off.size() - 1;
-    // the records lie side by side in pdus, so this many frames hold them all
-    const int64_t cap = ((int64_t)pdus.size() + (4 + label_len) * n) / (D - 14 - label_len) + 2;
-    out.resize((size_t)(cap * Lb));
-    const uint8_t none = 0;
+  Encap b = {"gse", "frame", (size_t)Lb, false, nullptr, nullptr, nullptr};
+  b.bound = [&](int64_t bytes, int64_t n) { return (bytes + (4 + label_len) * n) / (D - 14 - label_len) + 2; };
+  b.run = [&](const uint8_t *pdu, int64_t bytes, const uint32_t *off, int64_t n, uint8_t *out, int64_t cap, bool flush,
+              int64_t *units, int64_t *resume_pdu) {
     dvbt2ll_gse_result res;
-    if ((st = dvbt2ll_gse_run_host(enc, pdus.empty() ? &none : pdus.data(), (int64_t)pdus.size(), off.data(), nullptr, n,
-                                   &pos, out.data(), cap, eof, &res)))
-      break;
-    int64_t *a = &tot.pdus_in, *b = &res.pdus_in;
-    for (int i = 0; i < 9; i++) a[i] += b[i];
-    if (res.bbframes && std::fwrite(out.data(), (size_t)Lb, (size_t)res.bbframes, bb) != (size_t)res.bbframes) { st = -1; break; }
-    // continue from the resume position: drop the PDUs before it
-    const uint32_t cut = off[(size_t)res.resume.pdu];
-    pdus.erase(pdus.begin(), pdus.begin() + cut);
-    off.erase(off.begin(), off.begin() + (size_t)res.resume.pdu);
-    for (uint32_t &o : off) o -= cut;
+    const int e = dvbt2ll_gse_run_host(enc, pdu, bytes, off, nullptr, n, &pos, out, cap, flush, &res);
+    if (e) return e;
+    int64_t *a = &tot.pdus_in, *c = &res.pdus_in;
+    for (int i = 0; i < 9; i++) a[i] += c[i];
     pos = {0, res.resume.pdu_byte, res.resume.frag_id};
-    if (eof) break;
-    // nothing consumed and no room to read on (a short datagram with max_pdus skipped records behind it holds its
-    // open frame back for ever): give up, not loop
-    if (res.resume.pdu == 0 && res.bbframes == 0 && (pdus.size() >= chunk || off.size() > max_pdus)) {
-      std::fprintf(stderr, "dvbt2ll_tx: gse: no frame completes within %zu bytes / %zu records\n", pdus.size(), off.size() - 1);
-      st = -1;
-      break;
-    }
-  }
-  if (st) std::fprintf(stderr, "dvbt2ll_tx: gse run failed: %s\n", dvbt2ll_strerror(st));
-  std::fprintf(stderr, "dvbt2ll_tx: gse: pdus_in %lld, complete %lld, fragmented %lld, gse_packets %lld, skipped_len %lld, "
-               "skipped_type %lld, bbframes %lld, pad_bytes %lld, flushed %lld\n", (long long)tot.pdus_in,
-               (long long)tot.complete, (long long)tot.fragmented, (long long)tot.gse_packets, (long long)tot.skipped_len,
-               (long long)tot.skipped_type, (long long)tot.bbframes, (long long)tot.pad_bytes, (long long)tot.flushed);
-  if (fin != stdin) std::fclose(fin);
+    *units = res.bbframes;
+    *resume_pdu = res.resume.pdu;
+    return 0;
+  };
+  b.report = [&] {
+    std::fprintf(stderr, "dvbt2ll_tx: gse: pdus_in %lld, complete %lld, fragmented %lld, gse_packets %lld, skipped_len %lld, "
+                 "skipped_type %lld, bbframes %lld, pad_bytes %lld, flushed %lld\n", (long long)tot.pdus_in,
+                 (long long)tot.complete, (long long)tot.fragmented, (long long)tot.gse_packets, (long long)tot.skipped_len,
+                 (long long)tot.skipped_type, (long long)tot.bbframes, (long long)tot.pad_bytes, (long long)tot.flushed);
+  };
+  FILE *bb = encap_file(b, in_path);
   dvbt2ll_gse_destroy(enc);
-  if (st) { std::fclose(bb); return nullptr; }
-  std::rewind(bb);
   return bb;
 }
 

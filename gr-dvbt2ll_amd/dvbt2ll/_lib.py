@@ -269,6 +269,9 @@ class _T2miOutResult(ctypes.Structure):
 BLOCKS = ("bbheaderbch", "ldpc", "interleavermod", "framemapperfint", "pilotgenp1insert")
 PARAMS = {"bbheaderbch": _BbParams, "ldpc": _LdpcParams, "interleavermod": _ImParams,
           "framemapperfint": _FmParams, "pilotgenp1insert": _PgParams}
+PDU_BLOCKS = {"ule": (_UleParams, _UlePos, _UleResult, True), "mpe": (_MpeParams, _MpePos, _MpeResult, False),
+              "mpefec": (_MpeFecParams, _MpeFecPos, _MpeFecResult, False),
+              "gse": (_GseParams, _GsePos, _GseResult, True)}
 
 # every symbol include/dvbt2ll_hip.h declares (checked by the CPU test suite)
 EXPORTS = ["dvbt2ll_strerror", "dvbt2ll_version", "dvbt2ll_device_count", "dvbt2ll_abi_version", "dvbt2ll_abi_check"]
@@ -408,27 +411,15 @@ def lib():
                                              ctypes.POINTER(_ModeAdaptResult)]
     L.dvbt2ll_modeadapt_destroy.argtypes = [vp]
     L.dvbt2ll_modeadapt_destroy.restype = None
-    L.dvbt2ll_ule_create.argtypes = [ctypes.POINTER(_UleParams), ci, ctypes.POINTER(vp)]
-    L.dvbt2ll_ule_run_device.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(_UlePos), vp, i64, ci, vp]
-    L.dvbt2ll_ule_get_result.argtypes = [vp, ctypes.POINTER(_UleResult)]
-    L.dvbt2ll_ule_run_host.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(_UlePos), vp, i64, ci,
-                                       ctypes.POINTER(_UleResult)]
-    L.dvbt2ll_ule_destroy.argtypes = [vp]
-    L.dvbt2ll_ule_destroy.restype = None
-    L.dvbt2ll_mpe_create.argtypes = [ctypes.POINTER(_MpeParams), ci, ctypes.POINTER(vp)]
-    L.dvbt2ll_mpe_run_device.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(_MpePos), vp, i64, ci, vp]
-    L.dvbt2ll_mpe_get_result.argtypes = [vp, ctypes.POINTER(_MpeResult)]
-    L.dvbt2ll_mpe_run_host.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(_MpePos), vp, i64, ci,
-                                       ctypes.POINTER(_MpeResult)]
-    L.dvbt2ll_mpe_destroy.argtypes = [vp]
-    L.dvbt2ll_mpe_destroy.restype = None
-    L.dvbt2ll_mpefec_create.argtypes = [ctypes.POINTER(_MpeFecParams), ci, ctypes.POINTER(vp)]
-    L.dvbt2ll_mpefec_run_device.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(_MpeFecPos), vp, i64, ci, vp]
-    L.dvbt2ll_mpefec_get_result.argtypes = [vp, ctypes.POINTER(_MpeFecResult)]
-    L.dvbt2ll_mpefec_run_host.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(_MpeFecPos), vp, i64, ci,
-                                          ctypes.POINTER(_MpeFecResult)]
-    L.dvbt2ll_mpefec_destroy.argtypes = [vp]
-    L.dvbt2ll_mpefec_destroy.restype = None
+    # the four PDU-batch encapsulators: (params, pos, result, whether the run calls take a type array)
+    for b, (par, pos, res, types) in PDU_BLOCKS.items():
+        head = [vp, vp, i64, vp] + ([vp] if types else []) + [i64, ctypes.POINTER(pos), vp, i64, ci]
+        getattr(L, "dvbt2ll_%s_create" % b).argtypes = [ctypes.POINTER(par), ci, ctypes.POINTER(vp)]
+        getattr(L, "dvbt2ll_%s_run_device" % b).argtypes = head + [vp]
+        getattr(L, "dvbt2ll_%s_get_result" % b).argtypes = [vp, ctypes.POINTER(res)]
+        getattr(L, "dvbt2ll_%s_run_host" % b).argtypes = head + [ctypes.POINTER(res)]
+        getattr(L, "dvbt2ll_%s_destroy" % b).argtypes = [vp]
+        getattr(L, "dvbt2ll_%s_destroy" % b).restype = None
     L.dvbt2ll_tsmux_schedule.argtypes = [ctypes.POINTER(_TsMuxParams), vp]
     L.dvbt2ll_tsmux_ticks_per_period.argtypes = [ci, i64]
     L.dvbt2ll_tsmux_ticks_per_period.restype = i64
@@ -450,14 +441,7 @@ def lib():
     L.dvbt2ll_tsmux_destroy.restype = None
     L.dvbt2ll_psi_build.argtypes = [ctypes.POINTER(_PsiParams), vp, i64]
     L.dvbt2ll_psi_build.restype = i64
-    L.dvbt2ll_gse_create.argtypes = [ctypes.POINTER(_GseParams), ci, ctypes.POINTER(vp)]
     L.dvbt2ll_gse_params_from_chain.argtypes = [vp, ci, ctypes.POINTER(_GseParams)]
-    L.dvbt2ll_gse_run_device.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(_GsePos), vp, i64, ci, vp]
-    L.dvbt2ll_gse_get_result.argtypes = [vp, ctypes.POINTER(_GseResult)]
-    L.dvbt2ll_gse_run_host.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(_GsePos), vp, i64, ci,
-                                       ctypes.POINTER(_GseResult)]
-    L.dvbt2ll_gse_destroy.argtypes = [vp]
-    L.dvbt2ll_gse_destroy.restype = None
     L.dvbt2ll_t2mi_out_create.argtypes = [ctypes.POINTER(_T2miOutParams), ci, ctypes.POINTER(vp)]
     L.dvbt2ll_t2mi_out_params_from_chain.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(_T2miOutParams)]
     L.dvbt2ll_t2mi_out_ts_packets.argtypes = [vp, ci]

@@ -23,6 +23,7 @@ from typing import NamedTuple
 import numpy as np
 
 from ._lib import lib, check, _GseParams, _GsePos, _GseResult
+from ._pdu import PduEncapsulator
 
 COUNTERS = ("pdus_in", "complete", "fragmented", "gse_packets", "skipped_len", "skipped_type", "bbframes", "pad_bytes",
             "flushed")
@@ -50,7 +51,11 @@ def frame_bound(pdu_len, n_pdus, D, label_len):
     return (int(pdu_len) + (4 + label_len) * int(n_pdus)) // (D - 14 - label_len) + 2
 
 
-class GseEncapsulator:
+class GseEncapsulator(PduEncapsulator):
+    PREFIX, COUNTERS, HAS_TYPES = "gse", COUNTERS, True
+    CPOS, CRESULT, POS, RESULT = _GsePos, _GseResult, GsePos, GseResult
+    UNITS, OUT = "bbframes", "bb"
+
     def __init__(self, kbch=0, framesize=0, rate=0, chain=None, plp=0, sis_mis=1, isi=0, label=None,
                  max_pdu_bytes=1 << 22, max_pdus=1 << 16, device=0):
         """kbch (or framesize / rate) and sis_mis / isi -- or chain, plp: taken from a Chain's PLP.  label: 6 or 3
@@ -67,12 +72,10 @@ class GseEncapsulator:
         p.label_len = len(label)
         p.label[:len(label)] = list(label)
         p.max_pdu_bytes, p.max_pdus = int(max_pdu_bytes), int(max_pdus)
-        self._h = None
-        h = ctypes.c_void_p()
-        check(L.dvbt2ll_gse_create(ctypes.byref(p), int(device), ctypes.byref(h)), "gse create")
-        self._h = h
+        self._create(p, device)
         self.kbch = p.kbch or _kbch(p.framesize, p.rate)
         self.Lb, self.D = self.kbch // 8, self.kbch // 8 - 10
+        self.unit_bytes = self.Lb
         self.label, self.label_len, self.sis_mis, self.isi = label, len(label), p.sis_mis, p.isi
         self.max_pdu_bytes, self.max_pdus = p.max_pdu_bytes, p.max_pdus
 
@@ -85,52 +88,12 @@ class GseEncapsulator:
                    flush=False, stream=0):
         """asynchronous on stream: PDUs at device pointer pdu_ptr, n_pdus + 1 uint32 offsets at off_ptr (uint16
         types at type_ptr, or 0) -> BBFRAME k at out_ptr + Lb k"""
-        pos = _GsePos(*[int(x) for x in start])
-        check(lib().dvbt2ll_gse_run_device(self._h, ctypes.c_void_p(pdu_ptr), int(pdu_len), ctypes.c_void_p(off_ptr),
-                                           ctypes.c_void_p(type_ptr or None), int(n_pdus), ctypes.byref(pos),
-                                           ctypes.c_void_p(out_ptr), int(out_cap_blocks), int(bool(flush)),
-                                           ctypes.c_void_p(stream or None)), "gse run")
-
-    @staticmethod
-    def _result(raw):
-        return GseResult(GsePos(int(raw.resume.pdu), int(raw.resume.pdu_byte), int(raw.resume.frag_id)),
-                         {n: int(getattr(raw, n)) for n in COUNTERS})
-
-    def result(self):
-        """synchronises with the last run: its GseResult (the frames stay on the device)"""
-        raw = _GseResult()
-        check(lib().dvbt2ll_gse_get_result(self._h, ctypes.byref(raw)), "gse result")
-        return self._result(raw)
+        self._run_device(pdu_ptr, pdu_len, off_ptr, n_pdus, out_ptr, out_cap_blocks, type_ptr, start, flush, stream)
 
     def run(self, pdu, off, types=None, start=GsePos(), cap=None, flush=False):
         """host convenience (dvbt2ll_gse_run_host): pdu a uint8 array, off the n + 1 offsets, types the optional
         n protocol types; cap: capacity in BBFRAMEs (default: frame_bound, all that PDUs lying side by side become)"""
-        pdu = np.ascontiguousarray(pdu, np.uint8)
-        off = np.ascontiguousarray(off, np.uint32)
-        n = len(off) - 1
-        if types is not None:
-            types = np.ascontiguousarray(types, np.uint16)
-            if len(types) != n:
-                raise ValueError("one type per PDU")
-        if cap is None:
-            cap = self.frame_bound(len(pdu), n)
-        keep = pdu if len(pdu) else np.zeros(1, np.uint8)
-        out = np.zeros(max(1, int(cap)) * self.Lb, np.uint8)
-        raw = _GseResult()
-        pos = _GsePos(*[int(x) for x in start])
-        check(lib().dvbt2ll_gse_run_host(self._h, keep.ctypes.data_as(ctypes.c_void_p), len(pdu),
-                                         off.ctypes.data_as(ctypes.c_void_p),
-                                         types.ctypes.data_as(ctypes.c_void_p) if types is not None else None, n,
-                                         ctypes.byref(pos), out.ctypes.data_as(ctypes.c_void_p), int(cap),
-                                         int(bool(flush)), ctypes.byref(raw)), "gse run host")
-        res = self._result(raw)
-        res.bb = out[:res.counters["bbframes"] * self.Lb]
-        return res
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            lib().dvbt2ll_gse_destroy(self._h)
-            self._h = None
+        return self._run(pdu, off, types, start, cap, flush, self.frame_bound)
 
 
 def _kbch(framesize, rate):

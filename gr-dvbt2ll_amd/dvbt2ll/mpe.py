@@ -15,13 +15,13 @@ Example: datagrams on the device -> TS -> IQ, everything on torch's stream
     ch.run_device(ts_d.data_ptr(), 0, ts_d.numel(), 0, frames, iq_d.data_ptr(), st)
     res = enc.result()                     # synchronises: counters, resume position
 """
-import ctypes
 from dataclasses import dataclass
 from typing import NamedTuple
 
 import numpy as np
 
-from ._lib import lib, check, _MpeParams, _MpePos, _MpeResult
+from ._lib import _MpeParams, _MpePos, _MpeResult
+from ._pdu import PduEncapsulator
 
 COUNTERS = ("pdus_in", "sections", "skipped_len", "skipped_type", "mapped_macs", "ts_packets", "pusi_packets",
             "pad_bytes", "flushed")
@@ -44,7 +44,10 @@ class MpeResult:
     ts: np.ndarray = None
 
 
-class MpeEncapsulator:
+class MpeEncapsulator(PduEncapsulator):
+    PREFIX, COUNTERS = "mpe", COUNTERS
+    CPOS, CRESULT, POS, RESULT = _MpePos, _MpeResult, MpePos, MpeResult
+
     def __init__(self, pid=0x100, mac=MAC, mac_from_dest=False, packing=1, max_pdu_bytes=1 << 22, max_pdus=1 << 16,
                  device=0):
         """mac: the 6-byte MAC address the sections carry; mac_from_dest (mac_mode 1): a datagram to an IPv4 / IPv6
@@ -56,10 +59,7 @@ class MpeEncapsulator:
             raise ValueError("a MAC address is 6 bytes")
         p.mac[:] = list(bytes(mac))
         p.max_pdu_bytes, p.max_pdus = int(max_pdu_bytes), int(max_pdus)
-        self._h = None
-        h = ctypes.c_void_p()
-        check(lib().dvbt2ll_mpe_create(ctypes.byref(p), int(device), ctypes.byref(h)), "mpe create")
-        self._h = h
+        self._create(p, device)
         self.pid, self.mac, self.mac_mode, self.packing = p.pid, bytes(mac), p.mac_mode, p.packing
         self.max_pdu_bytes, self.max_pdus = p.max_pdu_bytes, p.max_pdus
 
@@ -73,44 +73,9 @@ class MpeEncapsulator:
                    stream=0):
         """asynchronous on stream: PDUs at device pointer pdu_ptr, n_pdus + 1 uint32 offsets at off_ptr -> TS packet
         k at out_ptr + 188 k"""
-        pos = _MpePos(*[int(x) for x in start])
-        check(lib().dvbt2ll_mpe_run_device(self._h, ctypes.c_void_p(pdu_ptr), int(pdu_len), ctypes.c_void_p(off_ptr),
-                                           int(n_pdus), ctypes.byref(pos), ctypes.c_void_p(out_ptr),
-                                           int(out_cap_packets), int(bool(flush)), ctypes.c_void_p(stream or None)),
-              "mpe run")
-
-    @staticmethod
-    def _result(raw):
-        return MpeResult(MpePos(int(raw.resume.pdu), int(raw.resume.section_byte), int(raw.resume.cc)),
-                         {n: int(getattr(raw, n)) for n in COUNTERS})
-
-    def result(self):
-        """synchronises with the last run: its MpeResult (the packets stay on the device)"""
-        raw = _MpeResult()
-        check(lib().dvbt2ll_mpe_get_result(self._h, ctypes.byref(raw)), "mpe result")
-        return self._result(raw)
+        self._run_device(pdu_ptr, pdu_len, off_ptr, n_pdus, out_ptr, out_cap_packets, 0, start, flush, stream)
 
     def run(self, pdu, off, start=MpePos(), cap=None, flush=False):
         """host convenience (dvbt2ll_mpe_run_host): pdu a uint8 array, off the n + 1 offsets; cap: capacity in TS
         packets (default: packet_bound, all that PDUs lying side by side become)"""
-        pdu = np.ascontiguousarray(pdu, np.uint8)
-        off = np.ascontiguousarray(off, np.uint32)
-        n = len(off) - 1
-        if cap is None:
-            cap = self.packet_bound(len(pdu), n)
-        keep = pdu if len(pdu) else np.zeros(1, np.uint8)
-        out = np.zeros(max(1, int(cap)) * 188, np.uint8)
-        raw = _MpeResult()
-        pos = _MpePos(*[int(x) for x in start])
-        check(lib().dvbt2ll_mpe_run_host(self._h, keep.ctypes.data_as(ctypes.c_void_p), len(pdu),
-                                         off.ctypes.data_as(ctypes.c_void_p), n, ctypes.byref(pos),
-                                         out.ctypes.data_as(ctypes.c_void_p), int(cap), int(bool(flush)),
-                                         ctypes.byref(raw)), "mpe run host")
-        res = self._result(raw)
-        res.ts = out[:res.counters["ts_packets"] * 188]
-        return res
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            lib().dvbt2ll_mpe_destroy(self._h)
-            self._h = None
+        return self._run(pdu, off, None, start, cap, flush, self.packet_bound)

@@ -16,13 +16,13 @@ Example: datagrams on the device -> TS -> IQ, everything on torch's stream
     ch.run_device(ts_d.data_ptr(), 0, ts_d.numel(), 0, frames, iq_d.data_ptr(), st)
     res = enc.result()                     # synchronises: counters, resume position
 """
-import ctypes
 from dataclasses import dataclass
 from typing import NamedTuple
 
 import numpy as np
 
-from ._lib import lib, check, _MpeFecParams, _MpeFecPos, _MpeFecResult
+from ._lib import _MpeFecParams, _MpeFecPos, _MpeFecResult
+from ._pdu import PduEncapsulator
 from .mpe import MAC
 
 COUNTERS = ("pdus_in", "sections", "fec_sections", "frames", "skipped_len", "skipped_type", "mapped_macs",
@@ -47,7 +47,10 @@ class MpeFecResult:
     ts: np.ndarray = None
 
 
-class MpeFecEncapsulator:
+class MpeFecEncapsulator(PduEncapsulator):
+    PREFIX, COUNTERS = "mpefec", COUNTERS
+    CPOS, CRESULT, POS, RESULT = _MpeFecPos, _MpeFecResult, MpeFecPos, MpeFecResult
+
     def __init__(self, pid=0x100, rows=1024, data_columns=191, rs_columns=64, mac=MAC, mac_from_dest=False, packing=1,
                  max_pdu_bytes=1 << 22, max_pdus=1 << 16, max_frames=64, device=0):
         """rows: 256, 512, 768 or 1024; data_columns (1 .. 191): the application data columns a frame may fill (fewer:
@@ -62,10 +65,7 @@ class MpeFecEncapsulator:
         p.mac[:] = list(bytes(mac))
         p.max_pdu_bytes, p.max_pdus = int(max_pdu_bytes), int(max_pdus)
         p.rows, p.data_columns, p.rs_columns, p.max_frames = int(rows), int(data_columns), int(rs_columns), int(max_frames)
-        self._h = None
-        h = ctypes.c_void_p()
-        check(lib().dvbt2ll_mpefec_create(ctypes.byref(p), int(device), ctypes.byref(h)), "mpefec create")
-        self._h = h
+        self._create(p, device)
         self.pid, self.mac, self.mac_mode, self.packing = p.pid, bytes(mac), p.mac_mode, p.packing
         self.rows, self.data_columns, self.rs_columns = p.rows, p.data_columns, p.rs_columns
         self.max_pdu_bytes, self.max_pdus, self.max_frames = p.max_pdu_bytes, p.max_pdus, p.max_frames
@@ -83,45 +83,9 @@ class MpeFecEncapsulator:
                    stream=0):
         """asynchronous on stream: PDUs at device pointer pdu_ptr, n_pdus + 1 uint32 offsets at off_ptr -> TS packet
         k at out_ptr + 188 k"""
-        pos = _MpeFecPos(*[int(x) for x in start])
-        check(lib().dvbt2ll_mpefec_run_device(self._h, ctypes.c_void_p(pdu_ptr), int(pdu_len),
-                                              ctypes.c_void_p(off_ptr), int(n_pdus), ctypes.byref(pos),
-                                              ctypes.c_void_p(out_ptr), int(out_cap_packets), int(bool(flush)),
-                                              ctypes.c_void_p(stream or None)), "mpefec run")
-
-    @staticmethod
-    def _result(raw):
-        r = raw.resume
-        return MpeFecResult(MpeFecPos(int(r.pdu), int(r.section), int(r.section_byte), int(r.cc), int(r.frame)),
-                            {n: int(getattr(raw, n)) for n in COUNTERS})
-
-    def result(self):
-        """synchronises with the last run: its MpeFecResult (the packets stay on the device)"""
-        raw = _MpeFecResult()
-        check(lib().dvbt2ll_mpefec_get_result(self._h, ctypes.byref(raw)), "mpefec result")
-        return self._result(raw)
+        self._run_device(pdu_ptr, pdu_len, off_ptr, n_pdus, out_ptr, out_cap_packets, 0, start, flush, stream)
 
     def run(self, pdu, off, start=MpeFecPos(), cap=None, flush=False):
         """host convenience (dvbt2ll_mpefec_run_host): pdu a uint8 array, off the n + 1 offsets; cap: capacity in TS
         packets (default: packet_bound)"""
-        pdu = np.ascontiguousarray(pdu, np.uint8)
-        off = np.ascontiguousarray(off, np.uint32)
-        n = len(off) - 1
-        if cap is None:
-            cap = self.packet_bound(len(pdu), n)
-        keep = pdu if len(pdu) else np.zeros(1, np.uint8)
-        out = np.zeros(max(1, int(cap)) * 188, np.uint8)
-        raw = _MpeFecResult()
-        pos = _MpeFecPos(*[int(x) for x in start])
-        check(lib().dvbt2ll_mpefec_run_host(self._h, keep.ctypes.data_as(ctypes.c_void_p), len(pdu),
-                                            off.ctypes.data_as(ctypes.c_void_p), n, ctypes.byref(pos),
-                                            out.ctypes.data_as(ctypes.c_void_p), int(cap), int(bool(flush)),
-                                            ctypes.byref(raw)), "mpefec run host")
-        res = self._result(raw)
-        res.ts = out[:res.counters["ts_packets"] * 188]
-        return res
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            lib().dvbt2ll_mpefec_destroy(self._h)
-            self._h = None
+        return self._run(pdu, off, None, start, cap, flush, self.packet_bound)

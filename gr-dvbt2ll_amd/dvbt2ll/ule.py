@@ -14,13 +14,13 @@ Example: datagrams on the device -> TS -> IQ, everything on torch's stream
     ch.run_device(ts_d.data_ptr(), 0, ts_d.numel(), 0, frames, iq_d.data_ptr(), st)
     res = enc.result()                     # synchronises: counters, resume position
 """
-import ctypes
 from dataclasses import dataclass
 from typing import NamedTuple
 
 import numpy as np
 
-from ._lib import lib, check, _UleParams, _UlePos, _UleResult
+from ._lib import _UleParams, _UlePos, _UleResult
+from ._pdu import PduEncapsulator
 
 COUNTERS = ("pdus_in", "sndus", "skipped_len", "skipped_type", "ts_packets", "pusi_packets", "pad_bytes", "flushed")
 MAC = bytes([0x02, 0x00, 0x48, 0x55, 0x4C, 0x4B])   # the reference flowgraph's destination address
@@ -41,7 +41,10 @@ class UleResult:
     ts: np.ndarray = None
 
 
-class UleEncapsulator:
+class UleEncapsulator(PduEncapsulator):
+    PREFIX, COUNTERS, HAS_TYPES = "ule", COUNTERS, True
+    CPOS, CRESULT, POS, RESULT = _UlePos, _UleResult, UlePos, UleResult
+
     def __init__(self, pid=0x100, dest=MAC, d_bit=None, packing=1, max_pdu_bytes=1 << 22, max_pdus=1 << 16,
                  device=0):
         """dest: the 6-byte destination address every SNDU carries, or None for none (D = 1; d_bit overrides).
@@ -54,10 +57,7 @@ class UleEncapsulator:
                 raise ValueError("a destination address is 6 bytes")
             p.dest[:] = list(bytes(dest))
         p.max_pdu_bytes, p.max_pdus = int(max_pdu_bytes), int(max_pdus)
-        self._h = None
-        h = ctypes.c_void_p()
-        check(lib().dvbt2ll_ule_create(ctypes.byref(p), int(device), ctypes.byref(h)), "ule create")
-        self._h = h
+        self._create(p, device)
         self.pid, self.d_bit, self.packing = p.pid, p.d_bit, p.packing
         self.max_pdu_bytes, self.max_pdus = p.max_pdu_bytes, p.max_pdus
 
@@ -71,49 +71,9 @@ class UleEncapsulator:
                    flush=False, stream=0):
         """asynchronous on stream: PDUs at device pointer pdu_ptr, n_pdus + 1 uint32 offsets at off_ptr (uint16
         types at type_ptr, or 0) -> TS packet k at out_ptr + 188 k"""
-        pos = _UlePos(*[int(x) for x in start])
-        check(lib().dvbt2ll_ule_run_device(self._h, ctypes.c_void_p(pdu_ptr), int(pdu_len), ctypes.c_void_p(off_ptr),
-                                           ctypes.c_void_p(type_ptr or None), int(n_pdus), ctypes.byref(pos),
-                                           ctypes.c_void_p(out_ptr), int(out_cap_packets), int(bool(flush)),
-                                           ctypes.c_void_p(stream or None)), "ule run")
-
-    @staticmethod
-    def _result(raw):
-        return UleResult(UlePos(int(raw.resume.pdu), int(raw.resume.sndu_byte), int(raw.resume.cc)),
-                         {n: int(getattr(raw, n)) for n in COUNTERS})
-
-    def result(self):
-        """synchronises with the last run: its UleResult (the packets stay on the device)"""
-        raw = _UleResult()
-        check(lib().dvbt2ll_ule_get_result(self._h, ctypes.byref(raw)), "ule result")
-        return self._result(raw)
+        self._run_device(pdu_ptr, pdu_len, off_ptr, n_pdus, out_ptr, out_cap_packets, type_ptr, start, flush, stream)
 
     def run(self, pdu, off, types=None, start=UlePos(), cap=None, flush=False):
         """host convenience (dvbt2ll_ule_run_host): pdu a uint8 array, off the n + 1 offsets, types the optional
         n Type fields; cap: capacity in TS packets (default: packet_bound, all that PDUs lying side by side become)"""
-        pdu = np.ascontiguousarray(pdu, np.uint8)
-        off = np.ascontiguousarray(off, np.uint32)
-        n = len(off) - 1
-        if types is not None:
-            types = np.ascontiguousarray(types, np.uint16)
-            if len(types) != n:
-                raise ValueError("one type per PDU")
-        if cap is None:
-            cap = self.packet_bound(len(pdu), n)
-        keep = pdu if len(pdu) else np.zeros(1, np.uint8)
-        out = np.zeros(max(1, int(cap)) * 188, np.uint8)
-        raw = _UleResult()
-        pos = _UlePos(*[int(x) for x in start])
-        check(lib().dvbt2ll_ule_run_host(self._h, keep.ctypes.data_as(ctypes.c_void_p), len(pdu),
-                                         off.ctypes.data_as(ctypes.c_void_p),
-                                         types.ctypes.data_as(ctypes.c_void_p) if types is not None else None, n,
-                                         ctypes.byref(pos), out.ctypes.data_as(ctypes.c_void_p), int(cap),
-                                         int(bool(flush)), ctypes.byref(raw)), "ule run host")
-        res = self._result(raw)
-        res.ts = out[:res.counters["ts_packets"] * 188]
-        return res
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            lib().dvbt2ll_ule_destroy(self._h)
-            self._h = None
+        return self._run(pdu, off, types, start, cap, flush, self.packet_bound)

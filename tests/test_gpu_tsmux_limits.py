@@ -1,4 +1,4 @@
-"""GPU: the TS multiplexer and its remux (csrc/tsmux_kernels.hip, the remux part of csrc/t2_capi.cpp) at the widths
+"""GPU: the TS multiplexer and its remux (csrc/tsmux_kernels.hip, the remux part of csrc/stream_capi.cpp) at the widths
 tests/tsmux_limit_cases.py takes them to -- eight live inputs, 64 map entries beside 64 tracked PIDs, calls past the
 emit and the classify kernel's grids, a seeded sweep -- against the sequential references: bytes, both counter sets and
 both resume positions, all exact.  Every run goes through the poisoned-buffer device_run of test_gpu_tsmux.py or
